@@ -8,8 +8,14 @@ the hot path over that batch: set_internal_states + 144 x forward() for every co
 launch with the time loop inside) + the basin-runoff reduction [T] (RCCL all-reduce when N > 1).
 Inputs are resident in HBM before the timed region.  Weak scaling: columns per GPU fixed.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds, on one GPU, the live VALU probe, the
+sub-records (fp64, mixed precision, configs[1], one column, configs[4] forward + backward, forcing streamed from the host) and
+the CPU baseline.  --dump-outputs DIR writes what the last timed step returned (see dump_outputs) for output-for-output
+comparisons of two builds.  The inputs are seeded, but the set-up re-draws the soils of the columns a build flags, so two builds
+run the same inputs only when their set-ups flag the same columns: the line's dumped_outputs.inputs_sha256 says whether they did.
 
 Without a launcher (`WORLD_SIZE` unset) and N > 1 the script starts its own N ranks, one fresh child process per GPU,
 BEFORE anything in this process touches the GPU.  Prints ONE JSON line on rank 0.
@@ -185,12 +191,22 @@ def parse_args(argv=None):
     ap.add_argument("--columns", type=int, default=1 << 20, help="columns per GPU")
     ap.add_argument("--tile", type=int, default=1, help="time tiling of the 144-row synth_1 forcing")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the fp64 / configs[1] sub-records and the VALU probe")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the live VALU probe, the sub-records (fp64, mixed precision, configs[1], "
+                         "one column, configs[4] forward + backward, forcing streamed from the host) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the sub-records and the VALU probe")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned to DIR/<name>.npy: basin_runoff [T] (fp64), and runoff, "
+                         "percolation [T, n], status [n] and the set-up's re-draws of their soils, redrawn [n], for a fixed "
+                         "seeded sample of n columns (rank 0's shard)")
     ap.add_argument("--workload", default="synth1", choices=["synth1", "phillipsburg"],
                     help="synth1 (default): BASELINE configs[2]/[3]; phillipsburg: configs[1], replicated Phillipsburg "
                          "column x 3000 hourly steps (use with --columns 10000 --dtype f64)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _free_port():
@@ -251,6 +267,52 @@ def wait_ranks(procs, poll_s=0.05):
         bad = [(r, rc) for r, rc in enumerate(rcs) if rc != 0]
         failed = bad[0] if bad else None
     return "".join(c for c in chunks if c), failed
+
+
+DUMP_COLUMNS = 16384  # columns sampled for --dump-outputs
+DUMP_SERIES_BYTES = 48 << 20  # ... fewer when the [T, n] series would exceed this (long T, fp64)
+
+
+def dump_columns(N, T, elem, n_series=2):
+    """Indices of the columns --dump-outputs writes: every column of a small job, else a fixed seeded sample (sorted), so that
+    two builds of the project write the same columns for the same arguments."""
+    import numpy as np
+    n = min(N, DUMP_COLUMNS, max(1, DUMP_SERIES_BYTES // (n_series * T * elem)))
+    if n == N:
+        return np.arange(N)
+    return np.sort(np.random.default_rng(0).choice(N, size=n, replace=False))
+
+
+def dump_outputs(outdir, series, basin, status, history, soils):
+    """series: {name: [T, N] device tensor}; basin: [T] fp64; status: [N] int32; history: [N] int64, the set-up iterations that
+    re-drew each column's soil (bit it-1 for iteration it); soils: the [L, N] soil parameter tensors the timed steps ran with.
+
+    Writes <name>.npy -- the series in the timed precision, basin, status and redrawn (= history) in fp64, all but basin for the
+    columns of dump_columns -- and returns {"files": {file: shape}, "inputs_sha256": digest of the soils of every column}.
+
+    Same arguments, same build: the same inputs.  Across builds the forcing is the same, but the soils are only where both builds'
+    set-ups flagged the same columns: the replacement soils of an iteration are drawn as one block for the flagged columns in
+    index order, so a column flagged by one build and not by the other shifts the soils of every column re-drawn after it in that
+    iteration (a flag can hinge on a psi tie at the 1e-8 level).  Equal inputs_sha256 means equal inputs; otherwise compare
+    redrawn.npy and expect the series of columns whose soils moved, and basin_runoff, to differ."""
+    import hashlib
+
+    import numpy as np
+    import torch
+    T, N = next(iter(series.values())).shape
+    idx = dump_columns(N, T, next(iter(series.values())).element_size(), len(series))
+    sel = torch.as_tensor(idx, device=status.device)
+    arrays = {nm: t.index_select(1, sel).cpu().numpy() for nm, t in series.items()}
+    arrays["basin_runoff"] = basin.double().cpu().numpy()
+    arrays["status"] = status.index_select(0, sel).double().cpu().numpy()
+    arrays["redrawn"] = history.index_select(0, sel).double().cpu().numpy()  # exact: 32 bits at most
+    h = hashlib.sha256()
+    for t in soils:
+        h.update(t.contiguous().cpu().numpy().tobytes())
+    os.makedirs(outdir, exist_ok=True)
+    for nm, a in arrays.items():
+        np.save(os.path.join(outdir, nm + ".npy"), a)
+    return {"files": {nm + ".npy": list(a.shape) for nm, a in arrays.items()}, "inputs_sha256": h.hexdigest()}
 
 
 def valu_probe_record(dev):
@@ -333,7 +395,8 @@ def main():
     N = args.columns
 
     def make_workload(kind, n_cols, dt, seed_rank, **eng_kw):
-        """(engine, precip[T, N], pet[T, N], redrawn) with inputs resident in HBM."""
+        """(engine, precip[T, N], pet[T, N], redrawn, history) with inputs resident in HBM; history[c] (int64) has bit it-1 set
+        when column c's soil was re-drawn in set-up iteration it."""
         if kind == "phillipsburg":
             g = np.load(os.path.join(ROOT, "tests", "golden", "phil_hourly_3000.npz"))  # first 3000 rows of the bundled forcing
             f = g["forcing"]
@@ -356,6 +419,7 @@ def main():
         # fp64, the reference's own arithmetic (which of the two flags a column hinges on a psi tie at the 1e-8 level),
         # so that every timed column is one the reference integrates to the end.
         redrawn = 0
+        history = torch.zeros(n_cols, dtype=torch.int64, device=dev)
         chk = None
         if kind != "phillipsburg":
             other = torch.float64 if dt == torch.float32 else torch.float32
@@ -377,6 +441,7 @@ def main():
             if bad.numel() == 0 or kind == "phillipsburg":
                 break
             redrawn += int(bad.numel())
+            history[bad] |= 1 << (it - 1)
             Q = W.perturbed_columns(int(bad.numel()), seed=(seed_rank + 1) * 100003 + it)
             for e in (eng, chk):
                 for k, t in (("alpha", e.alpha), ("n", e.n), ("ksat", e.ksat), ("theta_e", e.theta_e), ("theta_r", e.theta_r)):
@@ -384,9 +449,9 @@ def main():
         else:
             raise RuntimeError("bench set-up: %d columns still outside the reference's domain after 32 re-draws" % bad.numel())
         del chk, scratch
-        return eng, pr, pe, redrawn
+        return eng, pr, pe, redrawn, history
 
-    eng, precip, pet, resampled = make_workload(args.workload, N, dtype, rank)
+    eng, precip, pet, resampled, history = make_workload(args.workload, N, dtype, rank)
     T = precip.shape[0]
     out = {"runoff": torch.empty(T, N, dtype=dtype, device=dev), "percolation": torch.empty(T, N, dtype=dtype, device=dev)}
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
@@ -428,6 +493,12 @@ def main():
     if dist_on:
         all_reduce(faulted)
     geff_waves = eng.geff_wave_calls() / max(args.steps, 1)  # per launch
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, out, basin, eng.status, history,
+                              (eng.alpha, eng.n, eng.ksat, eng.theta_e, eng.theta_r, eng.thickness))
+    # a plain run stops at the headline: the probe, the sub-records and the CPU baseline each take runs of their own
+    extras = args.full and world == 1 and not args.no_extras
 
     if rank == 0:
         units = N * world * T * args.steps
@@ -470,11 +541,13 @@ def main():
             "faulted_columns": int(faulted.item()),
             "basin_runoff_total_cm": float(basin.sum().item()),
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         pmc = measured_valu(N, T, args.dtype)
         if pmc:
             line["valu_busy_frac"] = pmc.get("busy_frac")
         probe = {}
-        if world == 1 and not args.no_extras:
+        if extras:
             # compute-side roof, live: what this chip's vector ALU sustains vs what the Geff trapezoid (the dominant
             # instruction stream: 5 v_log/v_exp per node, 121 nodes per call) got out of it
             probe = valu_probe_record(dev)
@@ -499,11 +572,11 @@ def main():
             line["valu_roofline"] = vr
         elif pmc:
             line["valu_roofline"] = pmc
-        if world == 1 and not args.no_extras and args.workload == "synth1":
+        if extras and args.workload == "synth1":
             subs = {}
             # the parity-bearing precision on the same workload (1e-6 vs the reference holds in fp64)
             if args.dtype == "f32":
-                e64, p64, q64, _ = make_workload("synth1", N, torch.float64, rank)
+                e64, p64, q64, _, _ = make_workload("synth1", N, torch.float64, rank)
                 e64.geff_wave_calls()  # reset the counter
                 ms = []
                 for _ in range(3):
@@ -540,7 +613,7 @@ def main():
                 del e64, p64, q64
                 # fp64 column state with the fp32 hardware transcendentals inside the Geff trapezoid (LgarDims.geff_mode = 1):
                 # run totals of every column within 2e-6 of the native fp64 kernels', identical fault flags (tests/test_gpu_mixed.py)
-                emx, pmx, qmx, _ = make_workload("synth1", N, torch.float64, rank, geff_precision="f32")
+                emx, pmx, qmx, _, _ = make_workload("synth1", N, torch.float64, rank, geff_precision="f32")
                 ms = []
                 for _ in range(3):
                     emx.reset()
@@ -558,7 +631,7 @@ def main():
                     "faulted_columns": int((emx.status != 0).sum().item()),
                     "roofline_frac_hbm": alg_bytes_per_col_step(8, T) * N * T / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
                 del emx, pmx, qmx
-            ec, pc, qc, _ = make_workload("phillipsburg", 10_000, torch.float64, 0)
+            ec, pc, qc, _, _ = make_workload("phillipsburg", 10_000, torch.float64, 0)
             Tc = pc.shape[0]
             ms = []
             for _ in range(2):
@@ -579,7 +652,7 @@ def main():
             del ec
             # ... and in the mixed-precision mode (fp64 state, fp32-transcendental trapezoid nodes): its four-node groups are split
             # over the column's lanes as well (bit for bit the mixed mode with one lane per column)
-            em, _, _, _ = make_workload("phillipsburg", 10_000, torch.float64, 0, geff_precision="f32")
+            em, _, _, _, _ = make_workload("phillipsburg", 10_000, torch.float64, 0, geff_precision="f32")
             ms = []
             for _ in range(2):
                 em.reset()
@@ -740,7 +813,7 @@ def main():
             except Exception as e:  # noqa: BLE001 -- a sub-record must never take the headline line down
                 subs["streamed_host_forcing"] = {"error": "%s: %s" % (type(e).__name__, e)}
             line["sub_records"] = subs
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if dist_on:

@@ -43,6 +43,50 @@ def test_committed_pmc_lookup(monkeypatch):
     assert t is None and "another build" in why and b.measured_valu(1048576, 144, "f32") is None
 
 
+def test_options_and_dump_sample():
+    """A plain run is lean (--full off by default); --steps below 1 is refused; the dumped columns are a fixed seeded sample,
+    every column of a small job, and the dump stays within 64 MB."""
+    import numpy as np
+    import pytest
+    b = _bench()
+    a = b.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = b.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        b.parse_args(["--steps", "0"])
+    assert np.array_equal(b.dump_columns(1000, 144, 4), np.arange(1000))
+    for N, T, elem in ((1 << 20, 144, 4), (1 << 20, 144, 8), (10_000, 3000, 8), (1 << 20, 144 * 64, 8)):
+        idx = b.dump_columns(N, T, elem)
+        assert np.array_equal(idx, b.dump_columns(N, T, elem)) and np.array_equal(idx, np.unique(idx))
+        assert 0 < idx.size <= b.DUMP_COLUMNS and idx[-1] < N
+        assert 2 * T * elem * idx.size + 8 * T + 2 * 8 * idx.size <= 64 << 20
+
+
+def test_dump_writes_the_named_columns(tmp_path):
+    """dump_outputs gathers exactly the columns dump_columns names: every value encodes its own (step, column)."""
+    import numpy as np
+    import torch
+    b = _bench()
+    T, N, L = 5, 3 * b.DUMP_COLUMNS, 3
+    code = torch.arange(T * N, dtype=torch.float64).reshape(T, N)
+    series = {"runoff": code.float(), "percolation": -code}
+    status = torch.arange(N, dtype=torch.int32) % 7
+    history = torch.arange(N, dtype=torch.int64) % 5
+    soils = [torch.rand(L, N) for _ in range(6)]
+    d = b.dump_outputs(str(tmp_path), series, code.sum(1), status, history, soils)
+    idx = b.dump_columns(N, T, 4)
+    a = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert d["files"] == {nm + ".npy": list(x.shape) for nm, x in a.items()} and idx.size == b.DUMP_COLUMNS
+    assert a["runoff"].dtype == np.float32 and np.array_equal(a["runoff"], code.float().numpy()[:, idx])
+    assert np.array_equal(a["percolation"], -code.numpy()[:, idx])
+    assert np.array_equal(a["status"], idx % 7) and np.array_equal(a["redrawn"], idx % 5)
+    assert np.array_equal(a["basin_runoff"], code.sum(1).numpy())
+    # the digest covers every column's soils, not only the dumped ones
+    soils[2][1, np.setdiff1d(np.arange(N), idx)[0]] += 1
+    assert b.dump_outputs(str(tmp_path / "x"), series, code.sum(1), status, history, soils)["inputs_sha256"] != d["inputs_sha256"]
+
+
 def test_cpu_baseline_leg_runs_on_a_tiny_sample(monkeypatch):
     b = _bench()
     monkeypatch.setenv("LGAR_CPU_THREADS", "2")

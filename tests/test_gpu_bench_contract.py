@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -12,14 +13,18 @@ from conftest import ROOT
 pytestmark = pytest.mark.gpu
 
 
-def test_bench_json_contract():
+def _bench(*argv, timeout=600):
     env = dict(os.environ, LGAR_CPU_THREADS="4")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--columns", "8192"], capture_output=True, text=True, env=env, timeout=600)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + list(argv), capture_output=True, text=True, env=env,
+                       timeout=timeout)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1
-    d = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+def test_bench_json_contract():
+    d = _bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--columns", "8192", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -37,3 +42,43 @@ def test_bench_json_contract():
     units = 8192 * 144 * 2
     assert abs(d["value"] - units / (d["ms_per_step"] * 2e-3)) <= 1e-6 * d["value"]
     assert d["faulted_columns"] == 0
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full: the headline keys only (no probe, sub-records or CPU baseline); --steps sets the timed steps; --dump-outputs
+    writes the last timed step's outputs, the same ones run after run with the same arguments."""
+    N = 20000  # above the dump's column sample
+    runs = []
+    for k in range(2):
+        d = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--columns", str(N), "--dump-outputs", str(tmp_path / str(k)))
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and d["metric"] == "column-timesteps/sec"
+        assert abs(d["value"] - N * 144 * 3 / (d["ms_per_step"] * 3e-3)) <= 1e-6 * d["value"]
+        assert "cpu_baseline" not in d and "sub_records" not in d and "peak_v_exp_f32" not in d.get("valu_roofline", {})
+        a = {f[:-4]: np.load(tmp_path / str(k) / f) for f in sorted(os.listdir(tmp_path / str(k)))}
+        assert sorted(a) == ["basin_runoff", "percolation", "redrawn", "runoff", "status"]
+        assert sum(x.nbytes for x in a.values()) <= 64 << 20
+        n = a["status"].shape[0]
+        assert 0 < n < N and a["runoff"].shape == a["percolation"].shape == (144, n) and a["basin_runoff"].shape == (144,)
+        assert a["runoff"].dtype == np.float32 and a["basin_runoff"].dtype == np.float64 and a["status"].dtype == np.float64
+        assert d["dumped_outputs"]["files"] == {nm + ".npy": list(x.shape) for nm, x in a.items()}
+        assert abs(a["basin_runoff"].sum() - d["basin_runoff_total_cm"]) <= 1e-12 * abs(d["basin_runoff_total_cm"])
+        assert (a["status"] == 0).all() and a["runoff"].sum() > 0
+        # some sampled columns were re-drawn by the set-up (about a fifth of this ensemble), none more often than the total says
+        assert 0 < (a["redrawn"] > 0).sum() <= d["config"]["columns_redrawn_to_stay_in_reference_domain"]
+        runs.append((d, a))
+    assert runs[0][0]["dumped_outputs"]["inputs_sha256"] == runs[1][0]["dumped_outputs"]["inputs_sha256"]
+    for nm in runs[0][1]:
+        assert np.array_equal(runs[0][1][nm], runs[1][1][nm]), nm
+
+
+def test_dump_of_a_small_job_holds_every_column(tmp_path):
+    """A job of at most DUMP_COLUMNS columns is dumped whole: the dumped runoff summed over its columns is the device's own basin
+    reduction step by step, and the re-draw record accounts for every re-draw the set-up reports."""
+    N = 8192
+    d = _bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--columns", str(N), "--dump-outputs", str(tmp_path))
+    a = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert a["runoff"].shape == (144, N) and a["redrawn"].shape == (N,)
+    basin = a["basin_runoff"]
+    assert basin.sum() > 0 and np.allclose(a["runoff"].astype(np.float64).sum(1), basin, rtol=1e-9, atol=0)
+    bits = sum((a["redrawn"].astype(np.int64) >> k) & 1 for k in range(32))
+    assert bits.sum() == d["config"]["columns_redrawn_to_stay_in_reference_domain"] > 0
