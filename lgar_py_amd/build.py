@@ -15,8 +15,9 @@ UNITS = [("lgar_kernels.hip", [], ""), ("lgar_probe.hip", [], "")] + \
         [("lgar_kernels_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS] + \
         [("lgar_tangent_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS]
 SOURCES = sorted(set(u[0] for u in UNITS))
-HEADERS = ["lgar_device.hpp", "lgar_dual.hpp", "lgar_math.hpp", "lgar_host.hpp", "lgar_launch.hpp", "lgar_forward_body.hpp",
-           "lgar_tangent_body.hpp", "lgar_measure.hpp", os.path.join("..", "..", "include", "lgar.h")]
+# every header the units may include (taken from the directory: a header left off a hand-kept list would let a stale library
+# be reused after it changed)
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + [os.path.join("..", "..", "include", "lgar.h")]
 # -ffp-contract=off: expression rounding follows the reference's Python (no FMA contraction)
 # fp32 division stays correctly rounded: with the rcp-based fast divide x/x != 1, Se = (theta-theta_r)/(theta_e-theta_r)
 # exceeds 1 at saturation and 8 % of perturbed columns fault (measured), for no speed gain.

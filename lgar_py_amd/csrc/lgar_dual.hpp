@@ -2,12 +2,13 @@
 //
 // The reference differentiates dpLGAR.forward() with torch autograd over 0-d tensors
 // (/root/reference/dpLGAR/agents/DifferentiableLGAR.py:119,163).  Here the same device physics
-// (lgar_device.hpp, templated on the scalar type) is instantiated with Dual<R> = value + one
+// (lgar_column.hpp, templated on the scalar type) is instantiated with Dual<R> = value + one
 // tangent: control flow looks only at values, every arithmetic op carries d/dp along.
 // Derivative conventions follow torch: min() passes the gradient of the smaller argument (half
 // each on ties), abs() uses sign(x), pow() has d/dx = y x^(y-1) and d/dy = x^y ln x.
 #pragma once
-#include "lgar_device.hpp"
+// (all of the column physics first: the tangent path depends on the order in which the overloads below become visible)
+#include "lgar_column.hpp"
 
 namespace lgar {
 
@@ -29,7 +30,7 @@ template <typename R> __device__ __forceinline__ Dual<R> choose(bool c, const Du
 // third of the instructions of the IEEE divide, in kernels whose every instruction is on a lone wave's critical path); single
 // precision keeps its divide (the fp32 tangent kernels sit exactly at their register budget)
 template <typename R> __device__ __forceinline__ R dquot(R a, R b) {
-  if constexpr (sizeof(R) == 8) return a * fast_recip(b);
+  if constexpr (ScalarKind<R>::f64) return a * fast_recip(b);
   else return a / b;
 }
 
@@ -65,11 +66,11 @@ template <typename R> __device__ __forceinline__ Dual<R> pw(const Dual<R> &x, co
   if (x.v > R(0)) d = v * (y.d * (R(0.6931471805599453) * l2) + dquot(y.v * x.d, x.v));
   return Dual<R>(v, d);
 }
-// division policy (dv in lgar_device.hpp).  The VALUE of a quotient goes through exactly what the plain kernels' dv does with the
+// division policy (dv in lgar_scalar.hpp).  The VALUE of a quotient goes through exactly what the plain kernels' dv does with the
 // same policy (a tangent launch and the forward launch it differentiates must walk the same trajectory): in the double-precision
 // fast modes that is lean_div; the tangent reuses its refined reciprocal instead of dividing a second and a third time.
 template <int POL, typename R> __device__ __forceinline__ Dual<R> dv(const Dual<R> &a, const Dual<R> &b) {
-  if constexpr ((POL == 0 || POL == 3) && sizeof(R) == 8) {
+  if constexpr ((POL == POL_LEAN || POL == POL_MIXED) && ScalarKind<R>::f64) {
     const R q = lean_div(a.v, b.v);
     return Dual<R>(q, (a.d - q * b.d) * fast_recip(b.v));
   } else {
@@ -77,20 +78,20 @@ template <int POL, typename R> __device__ __forceinline__ Dual<R> dv(const Dual<
   }
 }
 template <int POL, typename R> __device__ __forceinline__ Dual<R> dv(const Dual<R> &a, R b) {
-  if constexpr ((POL == 0 || POL == 3) && sizeof(R) == 8) return Dual<R>(lean_div(a.v, b), a.d * fast_recip(b));
+  if constexpr ((POL == POL_LEAN || POL == POL_MIXED) && ScalarKind<R>::f64) return Dual<R>(lean_div(a.v, b), a.d * fast_recip(b));
   else return a / b;
 }
 template <int POL, typename R> __device__ __forceinline__ Dual<R> dv(R a, const Dual<R> &b) {
-  if constexpr ((POL == 0 || POL == 3) && sizeof(R) == 8) {
+  if constexpr ((POL == POL_LEAN || POL == POL_MIXED) && ScalarKind<R>::f64) {
     const R q = lean_div(a, b.v);
     return Dual<R>(q, -(q * b.d) * fast_recip(b.v));
   } else {
     return a / b;
   }
 }
-// verification mode (see pwx in lgar_device.hpp): correctly rounded pow / log for the value and the derivative
+// verification mode (see pwx in lgar_scalar.hpp): correctly rounded pow / log for the value and the derivative
 template <bool EX, typename R> __device__ __forceinline__ Dual<R> pwx(const Dual<R> &x, const Dual<R> &y) {
-  if constexpr (EX && sizeof(R) == 8) {
+  if constexpr (EX && ScalarKind<R>::f64) {
     const R v = pow(x.v, y.v);
     R d = R(0);
     if (x.v > R(0)) d = v * (y.d * log(x.v) + y.v * x.d / x.v);
@@ -111,7 +112,7 @@ template <typename R> __device__ __forceinline__ Dual<R> mn(const Dual<R> &a, co
   return Dual<R>(a.v, R(0.5) * (a.d + b.d));
 }
 
-// log2 / exp2 (the fused Geff node, lgar_device.hpp): d log2 x = dx / (x ln 2), d 2^y = 2^y ln 2 dy
+// log2 / exp2 (the fused Geff node, lgar_vg.hpp): d log2 x = dx / (x ln 2), d 2^y = 2^y ln 2 dy
 template <typename R> __device__ __forceinline__ Dual<R> lg2(const Dual<R> &x) {
   return Dual<R>(lg2(x.v), (x.v > R(0)) ? dquot(x.d, x.v * R(0.6931471805599453)) : R(0));
 }
@@ -128,7 +129,7 @@ template <typename R> __device__ __forceinline__ Dual<R> ex2p(const Dual<R> &y) 
   return Dual<R>(v, v * R(0.6931471805599453) * y.d);
 }
 // The fused Geff node for dual numbers: the value is computed by the same operations in the same order as the plain node
-// (lgar_device.hpp geff_node), the tangent in logarithmic form -- with a = x P, A = 1 + a, s = A^(-m/2), t = 1 - P s^2:
+// (lgar_vg.hpp geff_node), the tangent in logarithmic form -- with a = x P, A = 1 + a, s = A^(-m/2), t = 1 - P s^2:
 //   dln x = dx / x,  dln P = d(n-1) ln x + (n-1) dln x,  dln A = (a / A)(dln x + dln P),  dln s = d(-m/2) ln A - (m/2) dln A,
 //   dt = -P s^2 (dln P + 2 dln s),  dK = dKsat s t^2 + K dln s + 2 Ksat s t dt
 // (two reciprocals and ~25 multiply-adds per node instead of the ~60 operations of operator-by-operator propagation).

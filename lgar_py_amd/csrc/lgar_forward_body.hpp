@@ -11,7 +11,7 @@
 // the step index in the status word's upper bits; the next kernel of the chain picks exactly those columns up at that
 // step (waves without such a column exit at once).  Only the last kernel of the chain can report LGAR_ST_OVERFLOW.
 #pragma once
-#include "lgar_device.hpp"
+#include "lgar_column.hpp"
 
 namespace lgar {
 
@@ -48,7 +48,7 @@ template <typename R> struct KArgs {
 // every step: 8 of the 28 bytes per column and step the mixed-precision kernel still spilled in round 5).  Discharge is
 // the same sum as giuh_runoff.
 template <typename S, int FMAX> struct LdsSums {
-  static constexpr int rows = (FMAX <= LGAR_CAP_SMALL) ? (sizeof(S) == 8 ? 7 : 6) : 8;
+  static constexpr int rows = (FMAX <= LGAR_CAP_SMALL) ? (ScalarKind<S>::f64 ? 7 : 6) : 8;
 };
 
 // LDS row of accumulator j's per-call sum, or -1 if it stays in a register: with 6 rows the one left out is percolation
@@ -62,10 +62,10 @@ template <typename S, int FMAX, int SUMROWS = LdsSums<S, FMAX>::rows, int STRIDE
   unsigned char fl[FMAX][STRIDE];
   S sums[SUMROWS][STRIDE];
 };
-// the wave's LDS block of a forward kernel: one front table (and one row of sums) per lane, or (MODE 4) per group of
+// the wave's LDS block of a forward kernel: one front table (and one row of sums) per lane, or (MODE_COOP) per group of
 // cooperating lanes
 template <typename R, int FMAX, int MODE>
-using ForwardLDS = WaveLDS<R, FMAX, LdsSums<R, FMAX>::rows, coop_mode(MODE) ? LGAR_COOP_GROUPS : WAVE>;
+using ForwardLDS = WaveLDS<R, FMAX, LdsSums<R, FMAX>::rows, ModeTraits<R, MODE>::stride>;
 
 #ifndef LGAR_DEVSIM
 __device__ __forceinline__ double wave_sum(double v) {
@@ -173,7 +173,7 @@ __device__ __forceinline__ void store_state(const LGAR_KARG KArgs<R> &a, size_t 
   a.scalars[0 * N + c] = col.ponded_water;
   a.scalars[1 * N + c] = col.previous_precip;
   a.scalars[2 * N + c] = col.ending_volume;
-  if constexpr (!Column<R, NL, FMAX, MODE>::GIUH_MEM) {  // (GIUH_MEM: the queue lives there already)
+  if constexpr (!ModeTraits<R, MODE>::giuh_mem) {  // (giuh_mem: the queue lives there already)
 #pragma unroll
     for (int i = 0; i < LGAR_GMAX; i++) a.scalars[(3 + i) * N + c] = col.giuh_q[i];
   }
@@ -205,6 +205,7 @@ template <typename R, int NL, int FMAX, int MODE>
 __device__ __forceinline__ void forward_lane(const LGAR_KARG KArgs<R> *ap, size_t c, bool live, int lane,
                                              ForwardLDS<R, FMAX, MODE> &lds, bool leader = true, R *xchg = nullptr, int group = 0,
                                              int rank = 0) {
+  using M = ModeTraits<R, MODE>;
   const LGAR_KARG KArgs<R> &a = *ap;
   const size_t N = (size_t)a.N;
   const bool basin_on = (a.basin != nullptr) && (a.basin_mask != 0u);
@@ -219,13 +220,12 @@ __device__ __forceinline__ void forward_lane(const LGAR_KARG KArgs<R> *ap, size_
     if (any_lane(t_begin < a.T) == 0ull) return;  // nothing handed over to this wave
   }
   status &= LGAR_ST_FAULT_MASK;
-  LGAR_MEASURE_POINT(POISON_LDS, lds, coop_mode(MODE) ? group : lane)
+  LGAR_MEASURE_POINT(POISON_LDS, lds, M::coop ? group : lane)
   ColParams<R, NL> P;
   load_params<R, NL>(a, c, P);
-  // front-table slot: my own, or (MODE 4) my group's -- the lanes of a group hold the same column
-  constexpr int STRIDE = Column<R, NL, FMAX, MODE>::STRIDE;
-  const int slot = coop_mode(MODE) ? group : lane;  // (also my column of the LDS sums)
-  Column<R, NL, FMAX, MODE> col(P, &ap->G, make_view<R, FMAX, STRIDE>(&lds.f[0][0][0], &lds.fl[0][0], slot));
+  // front-table slot: my own, or (MODE_COOP) my group's -- the lanes of a group hold the same column
+  const int slot = M::coop ? group : lane;  // (also my column of the LDS sums)
+  Column<R, NL, FMAX, MODE> col(P, &ap->G, make_view<R, FMAX, M::stride>(&lds.f[0][0][0], &lds.fl[0][0], slot));
   // state HBM -> LDS / registers
   const int nf_stored = a.nf[c];
   const int cap = FMAX < a.F ? FMAX : a.F;
@@ -242,7 +242,7 @@ __device__ __forceinline__ void forward_lane(const LGAR_KARG KArgs<R> *ap, size_
   col.ponded_water = a.scalars[0 * N + c];
   col.previous_precip = a.scalars[1 * N + c];
   col.ending_volume = a.scalars[2 * N + c];
-  if constexpr (Column<R, NL, FMAX, MODE>::GIUH_MEM) {
+  if constexpr (M::giuh_mem) {
     col.giuh_mem = &a.scalars[3 * N + c];
     col.giuh_stride = N;
     R qsum = R(0);
@@ -279,7 +279,7 @@ __device__ __forceinline__ void forward_lane(const LGAR_KARG KArgs<R> *ap, size_
   // (fp64 kernels of the smallest capacity: t_stop is PARKED in scratch memory -- read at the top of every step, written at a
   // hand-over only.  In a register it lives across all of the column physics, and the allocator of these kernels, 60 registers
   // short, kept it by storing it to scratch at the top of every step: 4 of the 20 bytes per column and step still spilled.)
-  constexpr bool PARK = (sizeof(R) == 8) && (FMAX <= LGAR_CAP_SMALL) && !coop_mode(MODE);
+  constexpr bool PARK = M::f64 && (FMAX <= LGAR_CAP_SMALL) && !M::coop;
   LaneInt<PARK> t_stop_at;
   bool overflow_on_load = false;
   {
@@ -317,9 +317,9 @@ __device__ __forceinline__ void forward_lane(const LGAR_KARG KArgs<R> *ap, size_
   const int T = a.T;
   const size_t Nf = (size_t)a.Nf;
   const size_t cf = (Nf == N) ? c : (c / (size_t)a.Fg) % Nf;  // this column's forcing column
-  // (MODE 4, one wave per SIMD and registers to spare: the NEXT step's forcing is loaded a step ahead -- a lone wave has nothing
+  // (MODE_COOP, one wave per SIMD and registers to spare: the NEXT step's forcing is loaded a step ahead -- a lone wave has nothing
   // else to cover the ~1 us of that load with)
-  constexpr bool AHEAD = coop_mode(MODE);
+  constexpr bool AHEAD = M::coop;
   R precip_ahead = R(0), pet_ahead = R(0);
   if constexpr (AHEAD) {
     if (T > 0) {

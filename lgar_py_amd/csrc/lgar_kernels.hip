@@ -3,7 +3,7 @@
 // the known-answer tests.
 #include <hip/hip_runtime.h>
 
-#include "lgar_device.hpp"
+#include "lgar_geff.hpp"
 #include "lgar_host.hpp"
 #include "lgar_launch.hpp"
 
@@ -38,22 +38,22 @@ template <typename R> __global__ void lgar_leaf_kernel(LeafArgs<R> a) {
     case 3: r = h_from_se(l, x); break;
     case 4: r = geff(l, x, y, a.nint); break;
     case 5: r = aet_fn(l, y, a.z, x, a.wp_psi); break;
-    case 6: r = geff_literal<R, (sizeof(R) == 8) ? 1 : 0>(l, x, y, a.nint); break;
+    case 6: r = geff_literal<R, ScalarKind<R>::f64 ? POL_LIBRARY : POL_LEAN>(l, x, y, a.nint); break;
     case 7: r = lg2p(x); break;
     case 8: r = ex2p(x); break;
     case 9: r = pw(x, y); break;
     case 10:
-      if constexpr (sizeof(R) == 8) r = geff_mixed(l.alpha, l.n, l.m, l.inv_m, l.inv_n, l.ksat, l.te, l.tr, x, y, a.nint);
+      if constexpr (ScalarKind<R>::f64) r = geff_mixed(l.alpha, l.n, l.m, l.inv_m, l.inv_n, l.ksat, l.te, l.tr, x, y, a.nint);
       else r = geff(l, x, y, a.nint);
       break;
-    case 11: r = dv<0>(x, y); break;        // the fast modes' quotient (double precision: lean_div)
-    case 12: r = pwp<3>(x, y); break;       // the mixed-precision kernels' pow (pairwise-combined polynomials)
+    case 11: r = dv<POL_LEAN>(x, y); break;   // the fast modes' quotient (double precision: lean_div)
+    case 12: r = pwp<POL_MIXED>(x, y); break;  // the mixed-precision kernels' pow (pairwise-combined polynomials)
     case 13:
-      if constexpr (sizeof(R) == 8) r = lg2e(x);
+      if constexpr (ScalarKind<R>::f64) r = lg2e(x);
       else r = lg2p(x);
       break;
     case 14:
-      if constexpr (sizeof(R) == 8) r = ex2e(x);
+      if constexpr (ScalarKind<R>::f64) r = ex2e(x);
       else r = ex2p(x);
       break;
   }

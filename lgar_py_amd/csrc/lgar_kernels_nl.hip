@@ -29,7 +29,7 @@ namespace lgar {
 #define LGAR_OCC_F64_SMALL 2
 #endif
 template <typename R, int CAP> struct Occupancy {
-  static constexpr int waves = (sizeof(R) == 4) ? ((CAP <= LGAR_CAP_SMALL) ? LGAR_OCC_F32_SMALL : ((CAP <= LGAR_CAP_MID) ? 2 : 1))
+  static constexpr int waves = ScalarKind<R>::f32 ? ((CAP <= LGAR_CAP_SMALL) ? LGAR_OCC_F32_SMALL : ((CAP <= LGAR_CAP_MID) ? 2 : 1))
                                                 : ((CAP <= LGAR_CAP_SMALL) ? LGAR_OCC_F64_SMALL : 1);
 };
 
@@ -42,13 +42,13 @@ __global__ __launch_bounds__(WAVE) void lgar_init_kernel(KArgs<R> a) {
   init_lane<R, NL, CAP>((const LGAR_KARG KArgs<R> *)__builtin_amdgcn_kernarg_segment_ptr(), c, lane, lds);
 }
 
-// LDS tables through which cooperating lanes exchange trapezoid heads and nodes (lgar_device.hpp geff_nodes_cooperative,
+// LDS tables through which cooperating lanes exchange trapezoid heads and nodes (lgar_geff.hpp geff_nodes_cooperative,
 // geff_mixed_core<true>), sweep thetas and mass evaluations: one per group of lanes, in the cooperating-lanes kernels only
-// (MODE 4: native double-precision trapezoid, MODE 6: mixed-precision trapezoid).  With the front table kept once per group as
+// (MODE_COOP: native double-precision trapezoid, MODE_MIXED_COOP: mixed-precision trapezoid).  With the front table kept once per group as
 // well, a 32-front wave of such a kernel takes 34 KB of LDS (front table 17 KB, these tables 16.6 KB, the groups' sums): four
 // waves per CU, one per SIMD -- all a cooperating job may have.
 template <typename R, int MODE> struct CoopLDS {
-  static constexpr bool on = (sizeof(R) == 8) && coop_mode(MODE);
+  static constexpr bool on = ModeTraits<R, MODE>::coop_f64;
   R tab[on ? LGAR_COOP_GROUPS : 1][on ? LGAR_COOP_TAB_ROW : 1];
 };
 
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(WAVE, (Occupancy<R, CAP>::waves)) void lgar_forward
   __shared__ ForwardLDS<R, CAP, MODE> lds;
   __shared__ CoopLDS<R, MODE> coop_lds;
   const int lane = threadIdx.x;
-  // the argument block is read in place (kernarg segment), see LGAR_KARG in lgar_device.hpp
+  // the argument block is read in place (kernarg segment), see LGAR_KARG in lgar_scalar.hpp
   const LGAR_KARG KArgs<R> *ap = (const LGAR_KARG KArgs<R> *)__builtin_amdgcn_kernarg_segment_ptr();
   const size_t N = (size_t)ap->N;
   unsigned *ticket = ap->ticket;
@@ -154,31 +154,31 @@ static void launch_forward_kernel(KArgs<R> &a, unsigned nblocks, unsigned *ticke
   hipLaunchKernelGGL((lgar_forward_kernel<R, NL, CAP, MODE>), dim3(grid), dim3(WAVE), 0, st, a);
 }
 
-// fast-mode kernel of capacity CAP: MODE 1, or -- double precision with LgarDims.geff_mode = 1 -- MODE 3 (mixed-precision
-// trapezoid, lgar_device.hpp geff_mixed)
+// fast-mode kernel of capacity CAP: MODE_FAST, or -- double precision with LgarDims.geff_mode = 1 -- MODE_MIXED (mixed-precision
+// trapezoid, lgar_geff.hpp geff_mixed)
 template <typename R, int NL, int CAP>
 static void launch_fast_kernel(KArgs<R> &a, unsigned nblocks, unsigned *ticket, hipStream_t st, bool mixed) {
-  if constexpr (sizeof(R) == 8) {
+  if constexpr (ScalarKind<R>::f64) {
     if (mixed) {
-      if (a.coop > 1) {  // cooperating lanes with the mixed-precision trapezoid: the 32-front kernel only, as MODE 4
-        if constexpr (CAP == LGAR_FMAX) launch_forward_kernel<R, NL, CAP, 6>(a, nblocks, ticket, st);
+      if (a.coop > 1) {  // cooperating lanes with the mixed-precision trapezoid: the 32-front kernel only, as MODE_COOP
+        if constexpr (CAP == LGAR_FMAX) launch_forward_kernel<R, NL, CAP, MODE_MIXED_COOP>(a, nblocks, ticket, st);
         return;
       }
-      launch_forward_kernel<R, NL, CAP, 3>(a, nblocks, ticket, st);
+      launch_forward_kernel<R, NL, CAP, MODE_MIXED>(a, nblocks, ticket, st);
       return;
     }
   }
 #if defined(LGAR_MEASURE) && defined(LGAR_ONLY_MIXED)  // measurement builds that compile the mixed-precision kernels only
   (void)nblocks; (void)ticket; (void)st;
 #else
-  if constexpr (sizeof(R) == 8) {
+  if constexpr (ScalarKind<R>::f64) {
     if (a.coop > 1) {  // cooperating lanes: the 32-front kernel, whose LDS is per group of lanes (forward_typed)
-      if constexpr (CAP == LGAR_FMAX) launch_forward_kernel<R, NL, CAP, 4>(a, nblocks, ticket, st);
+      if constexpr (CAP == LGAR_FMAX) launch_forward_kernel<R, NL, CAP, MODE_COOP>(a, nblocks, ticket, st);
       return;
     }
   }
   (void)mixed;
-  launch_forward_kernel<R, NL, CAP, 1>(a, nblocks, ticket, st);
+  launch_forward_kernel<R, NL, CAP, MODE_FAST>(a, nblocks, ticket, st);
 #endif
 }
 
@@ -194,7 +194,7 @@ static int forward_typed(const LgarDims *dims, const LgarParams *params, LgarSta
 #if !(defined(LGAR_MEASURE) && (defined(LGAR_ONLY_MIXED) || defined(LGAR_ONLY_F32)))
   if (dims->search_mode == 0) {
     // the reference's literal searches: verification mode, one kernel at the full capacity
-    launch_forward_kernel<R, NL, LGAR_FMAX, 0>(a, grid, tickets, st);
+    launch_forward_kernel<R, NL, LGAR_FMAX, MODE_LITERAL>(a, grid, tickets, st);
     return launch_status();
   }
 #endif
@@ -203,9 +203,9 @@ static int forward_typed(const LgarDims *dims, const LgarParams *params, LgarSta
   const int need = NL + dims->num_subcycles + 2;
   // Jobs that cannot fill the chip (the reference's own use is ONE column, agents/DifferentiableLGAR.py:117-125): in double
   // precision every column gets 4..64 cooperating lanes that split the Geff trapezoid's nodes, the pows that open it and the
-  // front sweep's independent evaluations (lgar_device.hpp geff_nodes_cooperative / geff_ends_cooperative / coop_sweep_thetas /
+  // front sweep's independent evaluations (lgar_geff.hpp geff_nodes_cooperative / geff_ends_cooperative, lgar_column.hpp coop_sweep_thetas /
   // calc_dzdt_pairs).  Results are bit for bit those of one lane per column.  Such a job runs the 32-front kernel directly
-  // (MODE 4: front table and exchange table once per GROUP of lanes, 34 KB of LDS per wave, one wave per SIMD): no capacity
+  // (MODE_COOP: front table and exchange table once per GROUP of lanes, 34 KB of LDS per wave, one wave per SIMD): no capacity
   // chain, no hand-over.
   a.coop = cooperating_lanes<R>(dims, wave_slots(1));
   const bool tiny = (grid <= 1024u && dims->search_mode != 2) || a.coop > 1;  // search_mode 2: chain forced (tests)

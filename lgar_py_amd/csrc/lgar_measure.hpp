@@ -1,6 +1,6 @@
 // lgar_measure.hpp -- MEASUREMENT BUILDS ONLY (lgar_py_amd.build.build_variant passes -DLGAR_MEASURE; tools/ablate.py).
 //
-// Definitions of the measurement points the device code marks (lgar_device.hpp: LGAR_MEASURE_POINT, LGAR_ABLATABLE,
+// Definitions of the measurement points the device code marks (lgar_scalar.hpp: LGAR_MEASURE_POINT, LGAR_ABLATABLE,
 // LGAR_COUNT_GEFF_CALL).  The product library never includes this file: there the points are empty.
 //   -DLGAR_DUP_<X>     routine X runs twice on opaque copies of its inputs, results unchanged: the time difference to the
 //                      plain build is X's cost with the column dynamics (and so all other work) untouched
@@ -63,7 +63,7 @@ __device__ __forceinline__ double opaque(double x) { asm volatile("" : "+v"(x));
   LGAR_COUNT_IF_SITE(site) LGAR_COUNT_IF_SPARSE { if (LGAR_COUNT_WHO) status += (1 << LGAR_ST_STEP_SHIFT); }
 #ifdef LGAR_DUP_GEFF
 #define LGAR_POINT_DUP_GEFF(lk, theta1, theta2)                                                    \
-  if constexpr (sizeof(S) == sizeof(R)) {                                                          \
+  if constexpr (!M::dual) {                                                                         \
     const S extra = geff(lk, opaque(theta1), opaque(theta2), G->nint);                             \
     if (val(extra) == R(12345.678)) return extra; /* practically never true: keeps the duplicate alive */ \
   }
@@ -79,7 +79,7 @@ __device__ __forceinline__ double opaque(double x) { asm volatile("" : "+v"(x));
 #endif
 #ifdef LGAR_DUP_SEARCH
 #define LGAR_POINT_DUP_SEARCH(K, lk, psi, new_mass, prior_mass, dth, dthick, dth_k, dthick_k)      \
-  if constexpr (sizeof(S) == sizeof(R)) {                                                          \
+  if constexpr (!M::dual) {                                                                         \
     const S extra = theta_mass_balance<K>(lk, opaque(psi), opaque(new_mass), opaque(prior_mass), dth, dthick, dth_k, dthick_k); \
     if (val(extra) == R(-1.0)) status |= LGAR_ST_STRUCT; /* never true */                          \
   }
@@ -209,7 +209,7 @@ static __shared__ unsigned long long lgar_dbg_clk_last;
 // results differ from run to run.  Kept as a measurement variant to study that (tools/spill_determinism.sh).
 #ifdef LGAR_F32_HEADS_FROM_PSI
 #define LGAR_POINT_F32_HEADS_FROM_PSI(lk, i, g, ki, fronts_done)                                    \
-  if constexpr (sizeof(S) == 4 && sizeof(R) == 4 && MODE != 0) {                                   \
+  if constexpr (M::plain_f32 && !M::literal) {                                                      \
     if (!G->closed_form) {                                                                         \
       float kn_ = 0.0f;                                                                            \
       LGAR_COUNT_GEFF_CALL(1)                                                                      \

@@ -142,7 +142,7 @@ template <int OP> __device__ __forceinline__ void probe_body(float (&v)[8], f32x
     REP64(X)
 #undef X
   } else if (OP == LGAR_PROBE_GEFF_MIX) {
-    // the instruction stream of one iteration of the lean fp32 Geff loop (lgar_device.hpp geff<float>: two trapezoid
+    // the instruction stream of one iteration of the lean fp32 Geff loop (lgar_geff.hpp geff<float>: two trapezoid
     // nodes): 4 v_log + 4 v_exp + 3 v_pk_fma + 5 v_pk_mul + 2 v_pk_add, in program order with its dependences; four node
     // pairs = 72 instructions per probe iteration
 #define NODEPAIR(a, b)                                                                                 \

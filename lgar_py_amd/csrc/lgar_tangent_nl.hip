@@ -22,14 +22,14 @@ __host__ __device__ inline unsigned columns_per_block(int share) { return share 
 #define LGAR_TAN_F32_WAVES 2
 #endif
 template <typename R, int CAP> struct TangentOccupancy {
-  static constexpr int waves = (sizeof(R) == 4 && CAP == LGAR_CAP_SMALL) ? LGAR_TAN_F32_WAVES : 1;
+  static constexpr int waves = (ScalarKind<R>::f32 && CAP == LGAR_CAP_SMALL) ? LGAR_TAN_F32_WAVES : 1;
 };
 template <typename R, int NL, int CAP, int MODE>
 __global__ __launch_bounds__(WAVE, (TangentOccupancy<R, CAP>::waves)) void lgar_tangent_kernel(TArgs<R> a) {
   __shared__ WaveLDS<Dual<R>, CAP, 1> lds;
   __shared__ R xchg[LGAR_XCHG_WORDS];  // tangent_share: the lanes of a column exchange trapezoid nodes through it (lgar_dual.hpp)
   const int lane = threadIdx.x;
-  // the argument block is read in place (kernarg segment), see LGAR_KARG in lgar_device.hpp
+  // the argument block is read in place (kernarg segment), see LGAR_KARG in lgar_scalar.hpp
   const LGAR_KARG TArgs<R> *ap = (const LGAR_KARG TArgs<R> *)__builtin_amdgcn_kernarg_segment_ptr();
   if (ap->pending_in != nullptr && *ap->pending_in == 0u) return;  // no column was handed over to this kernel
   const size_t N = (size_t)ap->N;
@@ -85,21 +85,21 @@ static int tangent_typed(const LgarDims *dims, const LgarParams *params, const L
              (const R *)forcing->precip, (const R *)forcing->pet, (const R *)w_runoff, (const R *)w_perc,
              (R *)grad_out, (R *)tangent_runoff, status, make_glob<R>(dims)};
   if (dims->search_mode == 0) {
-    launch_one<R, NL, LGAR_FMAX, 0>(a, nblocks, tickets, st);
+    launch_one<R, NL, LGAR_FMAX, MODE_LITERAL>(a, nblocks, tickets, st);
     return launch_status();
   }
   const bool chain = (NL + dims->num_subcycles + 2 <= LGAR_CAP_SMALL) && (nblocks > 1024u || dims->search_mode == 2);
   if (chain) {
     a.chain_first = 1; a.chain_last = 0;
     a.pending_out = tickets ? tickets + 4 : nullptr;
-    launch_one<R, NL, LGAR_CAP_SMALL, 1>(a, nblocks, tickets, st);
+    launch_one<R, NL, LGAR_CAP_SMALL, MODE_FAST>(a, nblocks, tickets, st);
     int rc = launch_status();
     if (rc) return rc;
     a.chain_first = 0; a.chain_last = 1;
     a.pending_in = a.pending_out;
     a.pending_out = nullptr;
   }
-  launch_one<R, NL, LGAR_FMAX, 1>(a, nblocks, tickets ? tickets + 1 : nullptr, st);
+  launch_one<R, NL, LGAR_FMAX, MODE_FAST>(a, nblocks, tickets ? tickets + 1 : nullptr, st);
   return launch_status();
 }
 

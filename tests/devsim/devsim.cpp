@@ -1,6 +1,6 @@
 // devsim.cpp -- TEST INFRASTRUCTURE ONLY: the device code of lgar_py_amd/csrc compiled for the host.
 //
-// The column physics (lgar_device.hpp), the per-lane kernel bodies (lgar_forward_body.hpp, lgar_tangent_body.hpp) and the
+// The column physics (lgar_column.hpp), the per-lane kernel bodies (lgar_forward_body.hpp, lgar_tangent_body.hpp) and the
 // front-capacity chain are plain C++ templates; with -DLGAR_DEVSIM the few GPU intrinsics they use map to libm and
 // wave-level operations degenerate to a single lane.  This lets the CPU test suite (-m "not gpu") run the SAME source the
 // GPU executes against the reference's golden vectors, so logic errors surface without a GPU.  It is not a fallback: the
@@ -65,7 +65,7 @@ template <typename R, int NL, int CAP, int MODE> void run_forward(const KArgs<R>
 template <typename R, int NL>
 int forward_typed(const LgarDims *d, const LgarParams *p, LgarState *s, const LgarForcing *f, const LgarStepOut *o, int32_t *status) {
   KArgs<R> a = make_args<R>(d, p, s, f, o, status);
-  if (d->search_mode == 0) { run_forward<R, NL, LGAR_FMAX, 0>(a); return 0; }
+  if (d->search_mode == 0) { run_forward<R, NL, LGAR_FMAX, MODE_LITERAL>(a); return 0; }
   // same chain selection as lgar_kernels_nl.hip (search_mode 2 forces it; the simulator has no notion of a tiny grid)
   const int need = NL + d->num_subcycles + 2;
   const bool chain = d->search_mode == 2;
@@ -75,17 +75,17 @@ int forward_typed(const LgarDims *d, const LgarParams *p, LgarState *s, const Lg
   caps[nc++] = LGAR_FMAX;
   for (int i = 0; i < nc; i++) {
     a.chain_first = (i == 0); a.chain_last = (i == nc - 1);
-    if constexpr (sizeof(R) == 8) {
-      if (d->geff_mode == 1) {  // mixed-precision trapezoid (MODE 3)
-        if (caps[i] == LGAR_CAP_SMALL) run_forward<R, NL, LGAR_CAP_SMALL, 3>(a);
-        else if (caps[i] == LGAR_CAP_MID) run_forward<R, NL, LGAR_CAP_MID, 3>(a);
-        else run_forward<R, NL, LGAR_FMAX, 3>(a);
+    if constexpr (ScalarKind<R>::f64) {
+      if (d->geff_mode == 1) {  // mixed-precision trapezoid
+        if (caps[i] == LGAR_CAP_SMALL) run_forward<R, NL, LGAR_CAP_SMALL, MODE_MIXED>(a);
+        else if (caps[i] == LGAR_CAP_MID) run_forward<R, NL, LGAR_CAP_MID, MODE_MIXED>(a);
+        else run_forward<R, NL, LGAR_FMAX, MODE_MIXED>(a);
         continue;
       }
     }
-    if (caps[i] == LGAR_CAP_SMALL) run_forward<R, NL, LGAR_CAP_SMALL, 1>(a);
-    else if (caps[i] == LGAR_CAP_MID) run_forward<R, NL, LGAR_CAP_MID, 1>(a);
-    else run_forward<R, NL, LGAR_FMAX, 1>(a);
+    if (caps[i] == LGAR_CAP_SMALL) run_forward<R, NL, LGAR_CAP_SMALL, MODE_FAST>(a);
+    else if (caps[i] == LGAR_CAP_MID) run_forward<R, NL, LGAR_CAP_MID, MODE_FAST>(a);
+    else run_forward<R, NL, LGAR_FMAX, MODE_FAST>(a);
   }
   return 0;
 }
@@ -109,13 +109,13 @@ int tangent_typed(const LgarDims *d, const LgarParams *p, const LgarParams *dir,
              d->forcing_group > 1 ? d->forcing_group : 1, 0 /* one lane: nothing to share */, d->front_slots > 0 ? d->front_slots : LGAR_FMAX, nullptr, nullptr, nullptr, 1, 1, (const R *)p->alpha, (const R *)p->n, (const R *)p->ksat, (const R *)p->theta_e,
              (const R *)p->theta_r, (const R *)p->thickness, (const R *)dir->alpha, (const R *)dir->n, (const R *)dir->ksat,
              (const R *)f->precip, (const R *)f->pet, (const R *)wr, (const R *)wp, (R *)grad, (R *)tser, status, make_glob<R>(d)};
-  if (d->search_mode == 0) { run_tangent<R, NL, LGAR_FMAX, 0>(a); return 0; }
+  if (d->search_mode == 0) { run_tangent<R, NL, LGAR_FMAX, MODE_LITERAL>(a); return 0; }
   if (d->search_mode == 2 && NL + d->num_subcycles + 2 <= LGAR_CAP_SMALL) {
     a.chain_first = 1; a.chain_last = 0;
-    run_tangent<R, NL, LGAR_CAP_SMALL, 1>(a);
+    run_tangent<R, NL, LGAR_CAP_SMALL, MODE_FAST>(a);
     a.chain_first = 0; a.chain_last = 1;
   }
-  run_tangent<R, NL, LGAR_FMAX, 1>(a);
+  run_tangent<R, NL, LGAR_FMAX, MODE_FAST>(a);
   return 0;
 }
 
@@ -156,7 +156,7 @@ void devsim_geff(int variant, int n, const double *theta1, const double *theta2,
     l.ksat = ksat[i]; l.te = te[i]; l.tr = tr[i];
     if (variant == 0) out[i] = geff_fused<double>(l, theta1[i], theta2[i], nint);
     else if (variant == 1) out[i] = geff_mixed(l.alpha, l.n, l.m, l.inv_m, l.inv_n, l.ksat, l.te, l.tr, theta1[i], theta2[i], nint);
-    else if (variant == 2) out[i] = geff_literal<double, 1>(l, theta1[i], theta2[i], nint);
+    else if (variant == 2) out[i] = geff_literal<double, POL_LIBRARY>(l, theta1[i], theta2[i], nint);
     else {
       LayerK<float> f;
       f.alpha = (float)l.alpha; f.n = (float)l.n; f.m = 1.0f - 1.0f / f.n; f.inv_m = 1.0f / f.m; f.inv_n = 1.0f / f.n;

@@ -423,7 +423,7 @@ def test_nan_in_the_forcing_is_flagged():
 
 @pytest.mark.parametrize("name", ["rand03", "synth2_phil", "bench_col10707", "five_layer_synth1", "manyfronts_pulse_84"])
 def test_giuh_queue_in_place_survives_cut_launches_and_matches_the_reference_queue(name):
-    """The mixed-precision kernels update the GIUH queue in place in the `scalars` rows of the state (Column::GIUH_MEM) instead of
+    """The mixed-precision kernels update the GIUH queue in place in the `scalars` rows of the state (ModeTraits::giuh_mem) instead of
     carrying it in registers; the flag "something is queued" is rebuilt from those rows at every launch.  A run cut into four
     launches must equal the one-launch run bit for bit -- series, scalars, front table --, and at every cut the queue rows must
     hold the reference's own queue (lgar/giuh.py:8-20; fixtures: `giuh_queue[t]`): to 1e-9 in the native mode, to the

@@ -148,7 +148,7 @@ def test_mixed_precision_is_an_fp64_fast_mode_option():
 @pytest.mark.parametrize("name", ["rand03", "synth2_phil", "bench_col10707", "five_layer_synth1", "manyfronts_pulse_84"])
 def test_mixed_giuh_queue_in_place_equals_queue_in_registers(name):
     """The one-lane mixed-precision kernels (MODE 3) keep the GIUH queue in the column's rows of the `scalars` array and update it
-    there (lgar_device.hpp, Column::GIUH_MEM); the cooperating-lanes kernel (MODE 6) carries it in registers like every other
+    there (lgar_column.hpp, ModeTraits::giuh_mem); the cooperating-lanes kernel (MODE 6) carries it in registers like every other
     kernel.  Same additions in the same order: routed runoff, discharge, the stored queue and every other series must agree bit
     for bit -- in one launch, and when the run is cut into launches that each start from a queue left in memory by the last
     (the flag "something is queued" is then rebuilt from the loaded rows).  The routed runoff itself is checked against the

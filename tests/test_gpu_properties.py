@@ -237,7 +237,7 @@ def test_device_log2_exp2_pow_accuracy_on_hardware():
 
 
 def test_lean_division_and_pairwise_polynomials_on_hardware():
-    """The fast modes' double-precision quotient (v_rcp_f64 + one Newton step + one correction, lgar_device.hpp lean_div) against
+    """The fast modes' double-precision quotient (v_rcp_f64 + one Newton step + one correction, lgar_scalar.hpp lean_div) against
     the exact quotient: <= 1 ulp (2.3e-16 relative; measured 1.2e-16), over the magnitudes the column physics divides; and the
     mixed-precision kernels' log2 / exp2 / pow (high-order terms combined pairwise) to the bounds of the Horner forms."""
     import lgar_py_amd as lg

@@ -39,12 +39,12 @@ def kernels(src_root, tag, tmp):
 
 with tempfile.TemporaryDirectory() as tmp:
     old_root = os.path.join(tmp, "old")
-    for rel in ["include/lgar.h"] + ["lgar_py_amd/csrc/" + f for f in os.listdir(os.path.join(ROOT, "lgar_py_amd", "csrc"))
-                                      if f.endswith((".hpp", ".hip"))]:
-        p = subprocess.run(["git", "-C", ROOT, "show", "%s:%s" % (rev, rel)], capture_output=True)
-        if p.returncode == 0:
+    # the sources as they are at the revision (its headers, not the working tree's: files may have been added or removed since)
+    files = subprocess.check_output(["git", "-C", ROOT, "ls-tree", "-r", "--name-only", rev, "lgar_py_amd/csrc", "include"], text=True)
+    for rel in files.split():
+        if rel.endswith((".h", ".hpp", ".hip")):
             os.makedirs(os.path.dirname(os.path.join(old_root, rel)), exist_ok=True)
-            open(os.path.join(old_root, rel), "wb").write(p.stdout)
+            open(os.path.join(old_root, rel), "wb").write(subprocess.check_output(["git", "-C", ROOT, "show", "%s:%s" % (rev, rel)]))
     a, b = kernels(old_root, "old", tmp), kernels(ROOT, "new", tmp)
     for k in sorted(set(a) | set(b)):
         name = subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip().replace("void lgar::", "").split("(")[0]

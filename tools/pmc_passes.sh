@@ -6,6 +6,8 @@
 # Counters are collected in separate passes (8 SQ slots per pass; FETCH_SIZE and WRITE_SIZE cannot share one), with
 # --kernel-trace only, as MI355X_MICROARCH.md prescribes; a plain --kernel-trace --stats pass gives the kernel times.
 # Only the small CSVs are copied into OUTDIR (the raw rocprofv3 output stays in /tmp on the box).
+# Each pass runs under a time limit (PASS_TIMEOUT seconds, default 600); the first pass that fails or runs out of time ends
+# the script with its exit status: nothing more is started on a card that may have faulted.
 OUT=$1
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p "$ROOT/$OUT"
@@ -21,7 +23,13 @@ run() {  # run NAME WORKLOAD rocprof-args...
     mix) PROG="python3 $ROOT/tools/bench_mixed.py" ;;
   esac
   rm -rf /tmp/prof_$name
-  rocprofv3 --kernel-trace --output-format csv "$@" -d /tmp/prof_$name -o p -- $PROG > "$ROOT/$OUT/${wl}_$name.log" 2>&1 || echo "pass $name failed" >> "$ROOT/$OUT/${wl}_$name.log"
+  timeout -k 10 "${PASS_TIMEOUT:-600}" rocprofv3 --kernel-trace --output-format csv "$@" -d /tmp/prof_$name -o p -- $PROG \
+    > "$ROOT/$OUT/${wl}_$name.log" 2>&1
+  rc=$?
+  if [ $rc -ne 0 ]; then
+    echo "pass $name failed (exit status $rc)" | tee -a "$ROOT/$OUT/${wl}_$name.log"
+    exit $rc
+  fi
   mkdir -p "$ROOT/$OUT/${wl}_$name"
   find /tmp/prof_$name \( -name "*counter_collection.csv" -o -name "*kernel_stats.csv" \) -size -20M -exec cp {} "$ROOT/$OUT/${wl}_$name/" \;
   rm -rf /tmp/prof_$name
