@@ -169,6 +169,12 @@ template <typename S, int NL, int FMAX, int MODE> struct Column {
         return geff_mixed(val(lk.alpha), val(lk.n), val(lk.m), val(lk.inv_m), val(lk.inv_n), val(lk.ksat), val(lk.te), val(lk.tr),
                           theta1, theta2, G->nint);
     }
+#ifndef LGAR_NO_F32_RARE_GEFF
+    if constexpr (M::plain_f32 && !M::literal) {  // plain float: the rare sites (2 dry depth, 3 insert_water) share one out-of-line body
+      if (site != 1 && !G->closed_form)
+        return geff_f32_rare(lk.alpha, lk.n, lk.m, lk.inv_m, lk.inv_n, lk.te, lk.tr, theta1, theta2, G->nint);
+    }
+#endif
     return G->closed_form ? geff_closed<S, POL>(lk, theta1, theta2) : geff(lk, theta1, theta2, G->nint);
   }
   // calc_geff between two FRONTS of the table in the mixed-precision mode (calc_dzdt): the fronts' own psi are the trapezoid's
@@ -1478,6 +1484,16 @@ template <typename S, int NL, int FMAX, int MODE> struct Column {
         if (!fronts_done) {
           g = capillary_drive(lk, theta_1, theta_2, 1);
           ki = front_k(i, lk);
+#ifndef LGAR_NO_DZDT_MEMO
+          if constexpr (M::plain_f32 && !M::literal) {
+            // A SATURATED moving front that is the first of its layer: g is Geff(theta_{i+1} -> theta_e) of that layer, the very
+            // value insert_water asks for at the start of the next sub-step when this layer holds the free-drainage front (its
+            // theta_1 is the front after the layer's first).  Plain fp32 has one Geff function for all call sites, so the value
+            // is the one insert_water would compute, bit for bit: it goes into insert_water's memo.  (Fronts further down the
+            // layer are never that neighbour: they leave the memo alone.)
+            if (same_bits(theta_2, lk.te) && (i == 0 || F.layer(i - 1) != k)) { memo_theta = theta_1; memo_g = g; memo_layer = k; }
+          }
+#endif
         }
         if (is_nan(val(g))) status |= LGAR_ST_NAN;
         S dzdt;

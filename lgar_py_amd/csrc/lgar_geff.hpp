@@ -412,11 +412,28 @@ __device__ __forceinline__ float geff_f32_from_heads(const LayerK<float> &l, flo
     if (it & 1) accb = __builtin_elementwise_fma(sr, tt, accb);
     else acc = __builtin_elementwise_fma(sr, tt, acc);
   }
-#undef LGAR_GEFF_PAIR
   acc = acc + accb;
   float sum = acc.x + acc.y;
   if (M & 1) sum += node(__builtin_fmaf(float(M), dx, x0));
+#ifndef LGAR_NO_GEFF_ENDS
+  // the two END nodes as one more pair, checked as the loop above checks its pairs (K_r = ksat1 * 1 under the cut): every value
+  // goes through node()'s operations, the eight transcendentals as four packed steps instead of two dependent chains
+  float k0, kn;
+  {
+    const f32x2 xe = {x0, l.alpha * h_f};
+    f32x2 sr, tt;
+    LGAR_GEFF_PAIR(xe, sr, tt)
+    sr.x = (xe.x < xcut) ? ksat1 : sr.x;
+    tt.x = (xe.x < xcut) ? 1.0f : tt.x;
+    sr.y = (xe.y < xcut) ? ksat1 : sr.y;
+    tt.y = (xe.y < xcut) ? 1.0f : tt.y;
+    const f32x2 ke = sr * tt;
+    k0 = ke.x; kn = ke.y;
+  }
+#else
   const float k0 = node(x0), kn = node(l.alpha * h_f);
+#endif
+#undef LGAR_GEFF_PAIR
   if (kn_out != nullptr) *kn_out = kn;
   return fabsf((0.5f * dh) * ((k0 + kn) + 2.0f * sum));
 }
@@ -425,12 +442,35 @@ template <> __device__ __forceinline__ float geff<float>(const LayerK<float> &l,
   const float se_f = se_from_theta(l, theta2);
   // h(Se) of both end points (calc_h_from_se, utils.py:159-174) with one reciprocal of alpha
   const float inv_alpha = 1.0f / l.alpha;
+#ifndef LGAR_NO_GEFF_ENDS
+  // both heads statement by statement (each is a chain of two logarithms and two exponentials in which every operation waits
+  // for the one before it: see mixed_k_pair); the operations of head() below on the same operands
+  const float ni = -l.inv_m;
+  const float la = lg2(se_i), lb = lg2(se_f);
+  const float pa = ex2(ni * la), pb = ex2(ni * lb);
+  float ba = pa - 1.0f, bb = pb - 1.0f;
+  if (fabsf(ba) <= 1e-8f) ba = ba + 1e-12f;
+  if (fabsf(bb) <= 1e-8f) bb = bb + 1e-12f;
+  const float ua = lg2(ba), ub = lg2(bb);
+  const float oa = ex2(l.inv_n * ua), ob = ex2(l.inv_n * ub);
+  return geff_f32_from_heads(l, inv_alpha * oa, inv_alpha * ob, nint);
+#else
   auto head = [&](float se) {
     float base = pw(se, -l.inv_m) - 1.0f;
     if (fabsf(base) <= 1e-8f) base = base + 1e-12f;
     return inv_alpha * pw(base, l.inv_n);
   };
   return geff_f32_from_heads(l, head(se_i), head(se_f), nint);
+#endif
+}
+// geff<float>, NOT inlined: for the call sites of the plain fp32 kernels that run rarely (insert_water on a memo miss, the
+// dry-depth evaluation -- see geff_mixed, which does the same for the mixed-precision kernels, on why and on the scalar
+// arguments).  calc_dzdt, the hot site, keeps its inlined copy.  The same function on the same operands: the same values bit for
+// bit.  (Ksat cancels in G and is no argument.)
+__device__ __attribute__((noinline)) float geff_f32_rare(float alpha, float n, float m, float inv_m, float inv_n, float te, float tr,
+                                                         float theta1, float theta2, int nint) {
+  const LayerK<float> l{alpha, n, m, inv_m, inv_n, 1.0f, te, tr};
+  return geff<float>(l, theta1, theta2, nint);
 }
 template <> __device__ __forceinline__ double geff<double>(const LayerK<double> &l, double t1, double t2, int nint) {
   return geff_fused<double>(l, t1, t2, nint);

@@ -73,9 +73,43 @@ static int check_state(const LgarParams *p, const LgarState *s, const int32_t *s
 using namespace lgar;
 
 #ifdef LGAR_ONLY_LAYERS  // measurement variants (build.py build_variant): only these layer counts are linked in
+// (LGAR_ONLY_LAYERS is the layer counts' digits written together, e.g. 3 or 26: a count that is not among them has no
+// translation unit in the library and must not be referred to)
+#define LGAR_HAS_LAYERS(n)                                                                                        \
+  ((LGAR_ONLY_LAYERS) % 10 == n || (LGAR_ONLY_LAYERS) / 10 % 10 == n || (LGAR_ONLY_LAYERS) / 100 % 10 == n ||     \
+   (LGAR_ONLY_LAYERS) / 1000 % 10 == n || (LGAR_ONLY_LAYERS) / 10000 % 10 == n)
+#if LGAR_HAS_LAYERS(2)
+#define LGAR_CASE_2(FN, ...) case 2: return FN<2>(__VA_ARGS__);
+#else
+#define LGAR_CASE_2(FN, ...)
+#endif
+#if LGAR_HAS_LAYERS(3)
+#define LGAR_CASE_3(FN, ...) case 3: return FN<3>(__VA_ARGS__);
+#else
+#define LGAR_CASE_3(FN, ...)
+#endif
+#if LGAR_HAS_LAYERS(4)
+#define LGAR_CASE_4(FN, ...) case 4: return FN<4>(__VA_ARGS__);
+#else
+#define LGAR_CASE_4(FN, ...)
+#endif
+#if LGAR_HAS_LAYERS(5)
+#define LGAR_CASE_5(FN, ...) case 5: return FN<5>(__VA_ARGS__);
+#else
+#define LGAR_CASE_5(FN, ...)
+#endif
+#if LGAR_HAS_LAYERS(6)
+#define LGAR_CASE_6(FN, ...) case 6: return FN<6>(__VA_ARGS__);
+#else
+#define LGAR_CASE_6(FN, ...)
+#endif
 #define LGAR_BY_LAYERS(FN, ...)                        \
   switch (dims->n_layers) {                            \
-    case 3: return FN<3>(__VA_ARGS__);                 \
+    LGAR_CASE_2(FN, __VA_ARGS__)                       \
+    LGAR_CASE_3(FN, __VA_ARGS__)                       \
+    LGAR_CASE_4(FN, __VA_ARGS__)                       \
+    LGAR_CASE_5(FN, __VA_ARGS__)                       \
+    LGAR_CASE_6(FN, __VA_ARGS__)                       \
     default: return LGAR_E_ARG;                        \
   }
 #else

@@ -7,7 +7,20 @@
 //   -DLGAR_ABL_NO<X>   statement X is left out (what the register allocator / the schedule does without it)
 //   -DLGAR_COUNT_*     what the Geff-call counter counts (one call site, only sparse evaluations, lanes instead of waves)
 // The macros expand inside member functions of lgar::Column and use its members and the locals passed to them.
+//
+// Switches that turn one piece of the plain fp32 kernels' reuse OFF (each leaves every result bit for bit what it is with the
+// piece on; tools/ablate.py `reuse_*` variants, tests/test_devsim_f32_reuse.py, tests/test_gpu_f32_reuse.py).  The device code tests
+// them directly (#ifndef), so the simulator's build can pass them too:
+//   -DLGAR_NO_DZDT_MEMO        calc_dzdt does not hand Geff(theta_1 -> theta_e) of a saturated front to insert_water's memo
+//   -DLGAR_NO_F32_RARE_GEFF    insert_water and calc_dry_depth inline their own copies of the fp32 trapezoid (no geff_f32_rare)
+//   -DLGAR_NO_GEFF_ENDS        the fp32 trapezoid's end nodes and its two heads as single dependent chains
+//   -DLGAR_NO_F32_REUSE        all three
 #pragma once
+#ifdef LGAR_NO_F32_REUSE
+#define LGAR_NO_DZDT_MEMO
+#define LGAR_NO_F32_RARE_GEFF
+#define LGAR_NO_GEFF_ENDS
+#endif
 
 // (included from inside namespace lgar)
 __device__ __forceinline__ float opaque(float x) { asm volatile("" : "+v"(x)); return x; }

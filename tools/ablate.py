@@ -44,7 +44,15 @@ VARIANTS = {
     # mixed-precision kernels only (quick to build): experiments on geff_mixed, run with `ablate.py run mix`
     "mx_base": ["-DLGAR_ONLY_MIXED"], "mx_general": ["-DLGAR_ONLY_MIXED", "-DLGAR_GEFFM_GENERAL_ONLY"],
     "mx_regions": ["-DLGAR_ONLY_MIXED", "-DLGAR_COUNT_GEFFM_REGIONS"],
-    "f32_only": ["-DLGAR_ONLY_F32"], 
+    "f32_only": ["-DLGAR_ONLY_F32"],
+    # plain fp32 kernels: the reuse of Geff values item by item (switches: lgar_measure.hpp).  reuse_none is the kernel without
+    # any of it, reuse_<items> the kernel with only those (1 calc_dzdt -> insert_water memo, 2 out-of-line rare trapezoid,
+    # 4 trapezoid ends in lockstep); f32_only is all of them
+    "reuse_none": ["-DLGAR_ONLY_F32", "-DLGAR_NO_F32_REUSE"],
+    "reuse_1": ["-DLGAR_ONLY_F32", "-DLGAR_NO_F32_RARE_GEFF", "-DLGAR_NO_GEFF_ENDS"],
+    "reuse_2": ["-DLGAR_ONLY_F32", "-DLGAR_NO_DZDT_MEMO", "-DLGAR_NO_GEFF_ENDS"],
+    "reuse_12": ["-DLGAR_ONLY_F32", "-DLGAR_NO_GEFF_ENDS"],
+    "reuse_4": ["-DLGAR_ONLY_F32", "-DLGAR_NO_DZDT_MEMO", "-DLGAR_NO_F32_RARE_GEFF"],
     "mx_occ1": ["-DLGAR_ONLY_MIXED", "-DLGAR_OCC_F64_SMALL=1"],
     "mx_occ1_ilp": ["-DLGAR_ONLY_MIXED", "-DLGAR_OCC_F64_SMALL=1", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     "mx_ilp": ["-DLGAR_ONLY_MIXED", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
