@@ -216,6 +216,42 @@ int32_t lgar_forward_tangent(const LgarDims *dims, const LgarParams *params, con
                              void *grad_out, void *tangent_runoff, int32_t *status, int32_t dtype, void *stream,
                              uint32_t *tickets);
 
+/* Soil-moisture output: the water the front table holds in depth bins (the product the reference reserves and never fills:
+ * GlobalParams.soil_moisture_wetting_fronts, physics/GlobalParams.py:61; LGAR-C's soil_moisture_layers).  The theta profile
+ * implied by a front table is piecewise constant: front j (depth d_j, water content theta_j, layer tag k_j) reaches up to
+ * t_j = d_{j-1} when front j-1 carries the same layer tag, else to the top of layer k_j.  For bin i = [a, b]
+ *     S_i = sum_j theta_j * (clip(d_j, a, b) - clip(t_j, a, b)),   clip(x, a, b) = min(max(x, a), b)
+ * in front order, widths SIGNED (what Layer.mass_balance implies, layers/Layer.py:795-824: bins covering the column sum to
+ * ending_volume also in the steps where the reference leaves depths transiently non-monotone).  All arithmetic is fp64 whatever
+ * `dtype`, rounded once to it: a pure function of the stored state.
+ * edges: device fp64[n_bins + 1], cm, strictly increasing (the CALLER guarantees it: the library never reads device memory on
+ *   the host), 1 <= n_bins <= LGAR_MOIST_BINS; or NULL: the bins are each column's own soil layers and n_bins must equal
+ *   n_layers.
+ * what: 0 = mean volumetric water content S_i / w_i over the bin's in-column width w_i = clip(Z, a, b) - a (Z = the column's
+ *   total thickness); NaN where w_i <= 0 (bin wholly below the column).  1 = storage S_i in cm (0 below the column).
+ * out: [n_bins][n_columns] (dtype).
+ * basin: NULL, or device fp64[n_bins]: basin[i] += sum_c weights[c] * out[i][c] (weights: [n_columns] (dtype) or NULL = 1), by
+ *   the fixed-order pass LgarStepOut.basin uses for a stored series: the same bits on every run; the caller zeroes it.
+ * Only state->depth, theta, flags, n_fronts and params->thickness are read; nothing of the state is written.  n_fronts is
+ * clamped to the state's front_slots and layer tags to n_layers - 1, so the leftover state of a faulted column cannot index
+ * out of bounds (its output is not meaningful). */
+#define LGAR_MOIST_BINS 32
+int32_t lgar_soil_moisture(const LgarDims *dims, const LgarParams *params, const LgarState *state, const double *edges,
+                           int32_t n_bins, int32_t what, void *out, const void *weights, double *basin, int32_t dtype,
+                           void *stream);
+
+/* Run totals of a run cut into several lgar_forward calls.  lgar_forward sums a call's accumulators step by step from zero
+ * and adds that sum to LgarState.totals, so a chunked run adds several partial sums where one call adds one: the same numbers in
+ * another order, equal to the last bits only.  This replays the one-call order over series the chunks stored: for every j < 7
+ * with stored->series[j] != NULL ([n_rows][n_columns], dtype; only `series` of `stored` is read)
+ *     running[j][c] = (..((running[j][c] + series[j][0][c]) + series[j][1][c]) + ..) + series[j][n_rows - 1][c]
+ * running: [8][n_columns] (dtype), zeroed by the caller before the first chunk and carried from chunk to chunk; after the last
+ * one totals[j] = totals_before_the_run[j] + running[j] (j = 7, discharge, takes running[6]; percolation is not summed in
+ * bottom_mode 0) is what ONE call over all rows leaves, bit for bit, for every column that stayed in one kernel of the
+ * front-capacity chain (a hand-over inside a call splits that call's sum as well).  Rows a chunk did not write must read zero. */
+int32_t lgar_totals_replay(const LgarDims *dims, const LgarStepOut *stored, int32_t n_rows, void *running, int32_t dtype,
+                           void *stream);
+
 /* Leaf kernels (known-answer tests on the GPU), element-wise over n items:
  * op 0 theta_from_h(x), 1 se_from_h(x), 2 k_from_se(x), 3 h_from_se(x)      (physics/utils.py:35-174)
  * op 4 geff(theta1 = x, theta2 = y)                                        (lgar/green_ampt.py:45-84)

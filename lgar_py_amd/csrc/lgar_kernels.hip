@@ -6,6 +6,7 @@
 #include "lgar_geff.hpp"
 #include "lgar_host.hpp"
 #include "lgar_launch.hpp"
+#include "lgar_moisture.hpp"
 
 namespace lgar {
 
@@ -269,6 +270,33 @@ int32_t lgar_forward_tangent(const LgarDims *dims, const LgarParams *params, con
                  dtype, (hipStream_t)stream, tickets)
 }
 #endif
+
+int32_t lgar_soil_moisture(const LgarDims *dims, const LgarParams *params, const LgarState *state, const double *edges,
+                           int32_t n_bins, int32_t what, void *out, const void *weights, double *basin, int32_t dtype,
+                           void *stream) {
+  int rc = check_dims(dims);
+  if (rc) return rc;
+  if (!params || !params->thickness || !state || !state->depth || !state->theta || !state->flags || !state->n_fronts || !out)
+    return LGAR_E_ARG;
+  if (dtype != LGAR_F32 && dtype != LGAR_F64) return LGAR_E_ARG;
+  if (what != 0 && what != 1) return LGAR_E_ARG;
+  if (n_bins < 1 || n_bins > LGAR_MOIST_BINS || (!edges && n_bins != dims->n_layers)) return LGAR_E_ARG;
+  rc = launch_soil_moisture(dims, params, state, edges, n_bins, what, out, dtype, (hipStream_t)stream);
+  if (rc || !basin) return rc;
+  // [n_bins][n_columns] has the layout of a [T][n_columns] series: the stored-series pass, with its fixed summation order
+  if (dtype == LGAR_F64) launch_basin_reduce<double>(out, weights, basin, dims->n_columns, n_bins, (hipStream_t)stream);
+  else launch_basin_reduce<float>(out, weights, basin, dims->n_columns, n_bins, (hipStream_t)stream);
+  return launch_status();
+}
+
+int32_t lgar_totals_replay(const LgarDims *dims, const LgarStepOut *stored, int32_t n_rows, void *running, int32_t dtype,
+                           void *stream) {
+  int rc = check_dims(dims);
+  if (rc) return rc;
+  if (!stored || !running || n_rows < 0 || (dtype != LGAR_F32 && dtype != LGAR_F64)) return LGAR_E_ARG;
+  if (n_rows == 0) return 0;
+  return launch_totals_replay(dims, stored, n_rows, running, dtype, (hipStream_t)stream);
+}
 
 int32_t lgar_leaf_batch(int32_t op, int32_t n_items, const void *x, const void *y, double z, const void *alpha,
                         const void *n, const void *ksat, const void *theta_e, const void *theta_r, int32_t nint,

@@ -371,6 +371,137 @@ class LgarEngine:
                     k=self.k.cpu().numpy(), dzdt=self.dzdt.cpu().numpy(), layer=(fl & 0x7F).astype("int8"),
                     to_bottom=(fl >> 7).astype("int8"), n_fronts=self.n_fronts.cpu().numpy())
 
+    # ------------------------------------------------------------------------------------------
+    def _moisture_bins(self, edges, what):
+        """Host-side checks of soil_moisture's bins (the library never reads device memory on the host, so the C-ABI takes the
+        caller's word for the edges): returns (device fp64 edges or None, number of bins)."""
+        if self._state is None:
+            raise LgarError("this engine was created with with_state=False (tangent launches only)")
+        if what not in _capi.MOIST_WHAT:
+            raise LgarError("what must be 'theta' or 'storage' (got %r)" % (what,))
+        if edges is None:
+            return None, self.L
+        try:
+            e = torch.as_tensor(edges).detach().to("cpu", torch.float64)
+        except (TypeError, ValueError, RuntimeError) as err:
+            raise LgarError("edges must be a 1-D sequence of depths in cm (%s)" % err)
+        if e.dim() != 1 or e.numel() < 2:
+            raise LgarError("edges must be 1-D with at least two entries (got shape %s)" % (tuple(e.shape),))
+        if e.numel() - 1 > _capi.MOIST_BINS:
+            raise LgarError("at most %d bins (LGAR_MOIST_BINS); got %d" % (_capi.MOIST_BINS, e.numel() - 1))
+        if not bool(torch.isfinite(e).all()) or float(e[0]) < 0.0 or not bool((e[1:] > e[:-1]).all()):
+            raise LgarError("edges must be finite, >= 0 and strictly increasing")
+        return e.to(self.device).contiguous(), e.numel() - 1
+
+    def _moisture_launch(self, e_dev, n_bins, what, out, w, sums):
+        ptr = lambda t: None if t is None else t.data_ptr()
+        with torch.cuda.device(self.device):
+            rc = self.lib.lgar_soil_moisture(C.byref(self.dims), C.byref(self._params), C.byref(self._state), ptr(e_dev),
+                                             n_bins, _capi.MOIST_WHAT[what], out.data_ptr(), ptr(w), ptr(sums), self._dt,
+                                             self._stream())
+        _capi.check(rc, "lgar_soil_moisture")
+
+    def _moisture_weights(self, weights):
+        if weights is None:
+            return None
+        w = torch.as_tensor(weights).to(self.device, self.dtype).contiguous()
+        if tuple(w.shape) != (self.N,):
+            raise LgarError("weights must be [N]")
+        return w
+
+    def soil_moisture(self, edges=None, what="theta", out=None, weights=None, basin=False):
+        """Depth-binned water content of every column as the front table stands now (lgar_soil_moisture, include/lgar.h;
+        DESIGN.md section 9 has the definition): computed on the device from the stored state, nothing is copied to the host.
+
+        edges: [D + 1] depths in cm (finite, >= 0, strictly increasing, D <= 32) -> [D, N]; None = each column's own soil
+        layers -> [L, N].  what: "theta" = mean volumetric water content of the bin over its in-column width (NaN for a bin
+        wholly below the column), "storage" = cm of water in the bin.  The arithmetic is fp64 whatever the engine's dtype; the
+        result is rounded once to it.  out: optional [D, N] buffer (engine dtype and device, contiguous).
+        basin: True -> also returns the fp64 [D] sums over the columns, sum_c weights[c] * result[:, c] (weights [N], default 1),
+        in a fixed order (the same bits on every run); an fp64 [D] device tensor -> the sums are ADDED to it (like
+        LgarStepOut.basin) and it is returned.  Columns with a non-zero status hold leftover state: their entries are not
+        meaningful (never out of bounds)."""
+        e_dev, D = self._moisture_bins(edges, what)
+        if out is None:
+            out = torch.empty(D, self.N, dtype=self.dtype, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != (D, self.N) or out.dtype != self.dtype
+              or out.device != self.totals.device or not out.is_contiguous()):
+            raise LgarError("out must be a contiguous [%d, %d] %s tensor on %s" % (D, self.N, self.dtype, self.device))
+        w = self._moisture_weights(weights)
+        sums = None
+        if basin is True:
+            sums = torch.zeros(D, dtype=torch.float64, device=self.device)
+        elif basin is not False and basin is not None:
+            sums = basin
+            if (not isinstance(sums, torch.Tensor) or tuple(sums.shape) != (D,) or sums.dtype != torch.float64
+                    or sums.device != self.totals.device or not sums.is_contiguous()):
+                raise LgarError("basin must be True or a contiguous fp64 [%d] tensor on %s" % (D, self.device))
+        elif w is not None:
+            raise LgarError("weights are used by the basin sums only: pass basin=True")
+        self._moisture_launch(e_dev, D, what, out, w, sums)
+        return out if sums is None else (out, sums)
+
+    def run_with_soil_moisture(self, precip, pet, every, edges=None, what="theta", series=("runoff", "percolation"), basin=(),
+                               weights=None, check=True, forcing_group=1):
+        """forward() over the whole forcing with a soil-moisture snapshot after every `every` rows: the run is cut into windows
+        of `every` rows, each advanced by forward() on the row slice (series written straight into [T, N] buffers, basin rows
+        concatenated), and soil_moisture(edges, what) is taken after each full window.  Returns what forward() returns plus
+        "soil_moisture": [T // every, D, N]; row r is the state after step (r + 1) * every - 1.  Rows beyond the last full
+        window are still integrated.  Series, basin sums, the state and the status are those of ONE forward() over the same
+        forcing bit for bit.  So are the run totals: forward() adds a call's own sum to them, which over several windows is
+        another summation order, so the windows also store the accumulators that feed the totals (scratch series of `every`
+        rows for those the caller did not ask for) and lgar_totals_replay adds them up in the one-call order (include/lgar.h;
+        exact for every column that stays in one kernel of the front-capacity chain)."""
+        every = int(every)
+        if every < 1:
+            raise LgarError("every must be >= 1")
+        e_dev, D = self._moisture_bins(edges, what)
+        precip = torch.as_tensor(precip).to(self.device, self.dtype).contiguous()
+        pet = torch.as_tensor(pet).to(self.device, self.dtype).contiguous()
+        if precip.dim() == 1:
+            precip, pet = precip[None, :], pet[None, :]
+        self._set_forcing_layout(precip, pet, forcing_group)
+        T = precip.shape[0]
+        series = tuple(series)
+        # (zeros: a row no kernel writes -- a column that had faulted before the window -- must read zero in the replay)
+        res = {nm: torch.zeros(T, self.N, dtype=self.dtype, device=self.device) for nm in series}
+        # the accumulators forward() sums into the totals (lgar_forward_body.hpp: percolation only with a percolating bottom)
+        summed = [nm for j, nm in enumerate(ACC_NAMES[:7]) if not (j == 5 and self.dims.bottom_mode == 0)]
+        scratch = {nm: torch.zeros(min(every, T), self.N, dtype=self.dtype, device=self.device) for nm in summed if nm not in res}
+        before = self.totals[:8].clone()
+        running = torch.zeros(8, self.N, dtype=self.dtype, device=self.device)
+        snaps = torch.empty(T // every, D, self.N, dtype=self.dtype, device=self.device)
+        rows = {nm: [] for nm in basin}
+        for lo in range(0, T, every):
+            hi = min(lo + every, T)
+            if lo:
+                for buf in scratch.values():
+                    buf.zero_()
+            out = {nm: res[nm][lo:hi] for nm in series}
+            out.update({nm: buf[:hi - lo] for nm, buf in scratch.items()})
+            o = self.forward(precip[lo:hi], pet[lo:hi], series=series + tuple(scratch), out=out, check=False, basin=basin,
+                             weights=weights, forcing_group=forcing_group)
+            for nm in basin:
+                rows[nm].append(o["basin:" + nm])
+            stored = _capi.LgarStepOut()
+            for nm in summed:
+                stored.series[ACC_NAMES.index(nm)] = out[nm].data_ptr()
+            with torch.cuda.device(self.device):
+                rc = self.lib.lgar_totals_replay(C.byref(self.dims), C.byref(stored), hi - lo, running.data_ptr(), self._dt,
+                                                 self._stream())
+            _capi.check(rc, "lgar_totals_replay")
+            if hi - lo == every:
+                self._moisture_launch(e_dev, D, what, snaps[lo // every], None, None)
+        if T:
+            running[7] = running[6]  # discharge gains what giuh_runoff gains (models/dpLGAR.py:293-297)
+            self.totals[:8] = before + running
+        for nm in basin:
+            res["basin:" + nm] = torch.cat(rows[nm]) if rows[nm] else torch.zeros(0, dtype=torch.float64, device=self.device)
+        res["soil_moisture"] = snaps
+        if check:
+            self.check_status()
+        return res
+
     def total(self, name):
         return self.totals[ACC_NAMES.index(name)]
 

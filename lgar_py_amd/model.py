@@ -261,6 +261,13 @@ class dpLGAR(nn.Module):
                      dzdt=float(fr["dzdt"][i, column]), layer_num=int(fr["layer"][i, column]),
                      to_bottom=bool(fr["to_bottom"][i, column])) for i in range(nf)]
 
+    def soil_moisture(self, edges=None, what="theta"):
+        """Depth-binned water content as the front table stands now (LgarEngine.soil_moisture; the slot the reference
+        reserves as GlobalParams.soil_moisture_wetting_fronts, physics/GlobalParams.py:61): edges [D + 1] in cm -> [D, N],
+        None = the soil layers -> [L, N]; one column gives [D] / [L], like ending_volume.  fp64 on the accumulators' device."""
+        sm = self.engine.soil_moisture(edges, what).to(self.attr_device, torch.float64)
+        return sm[:, 0] if self.n_columns == 1 else sm
+
     def print_params(self):
         for nm, pl in (("Alpha", self.alpha), ("n", self.n), ("Ksat", self.ksat)):
             for i, p in enumerate(pl):
