@@ -55,6 +55,24 @@ class LgarStepOut(C.Structure):
     _fields_ = [("series", C.c_void_p * NACC), ("basin", C.c_void_p), ("weights", C.c_void_p), ("basin_mask", C.c_uint32), ("reserved", C.c_uint32), ("counters", C.c_void_p), ("call_sums", C.c_void_p)]
 
 
+def make_dims(*, n_columns, n_layers, dt_h=1.0, num_subcycles=1, initial_psi=2000.0, ponded_depth_max=0.0,
+              wilting_point_psi=15495.0, frozen_factor=1.0, nint=120, giuh_ordinates=(0.06, 0.51, 0.28, 0.12, 0.03), iter_cap=0,
+              search_mode=1, bottom_mode=0, use_closed_form_G=False, front_slots=None, geff_mode=0, forward_lanes=0):
+    """A filled LgarDims for an engine's keywords (LgarEngine's names; n_steps and the forcing layout are per call).  Plain
+    assignments: the caller has checked what it wants checked."""
+    d = LgarDims()
+    d.n_columns, d.n_layers, d.n_steps, d.num_subcycles = n_columns, n_layers, 0, int(num_subcycles)
+    d.nint, d.n_giuh, d.search_mode = int(nint), len(giuh_ordinates), int(search_mode)
+    d.dt_h, d.initial_psi, d.ponded_depth_max = float(dt_h), float(initial_psi), float(ponded_depth_max)
+    d.wilting_point_psi, d.frozen_factor = float(wilting_point_psi), float(frozen_factor)
+    for i, g in enumerate(giuh_ordinates):
+        d.giuh[i] = float(g)
+    d.iter_cap, d.bottom_mode, d.use_closed_form_G = int(iter_cap), int(bottom_mode), int(bool(use_closed_form_G))
+    d.geff_mode, d.forward_lanes = int(geff_mode), int(forward_lanes)
+    d.front_slots = int(front_slots) if front_slots else FMAX
+    return d
+
+
 class LgarError(RuntimeError):
     pass
 

@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.environ.get("LGAR_LIB") or os.path.join(CSRC, "liblgar_hip.so")
-LAYERS = (2, 3, 4, 5, 6)  # LGAR_LMIN .. LGAR_LMAX: one translation unit per soil-layer count and kernel family
+LAYERS = (2, 3, 4, 5, 6)  # LGAR_LAYERS (csrc/lgar_plan.hpp): one translation unit per soil-layer count and kernel family
 # (source, extra flags, object suffix)
 UNITS = [("lgar_kernels.hip", [], ""), ("lgar_probe.hip", [], ""), ("lgar_moisture.hip", [], "")] + \
         [("lgar_kernels_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS] + \
@@ -131,7 +131,7 @@ def build_variant(name, extra_flags, verbose=False, layers=(3,), tangent=False):
     if not tangent:
         units = [u for u in units if u[0] != "lgar_tangent_nl.hip"]
     # -DLGAR_MEASURE: the measurement points of the device code take their definitions from csrc/lgar_measure.hpp
-    flags = list(extra_flags) + ["-DLGAR_MEASURE", "-DLGAR_ONLY_LAYERS=%s" % "".join(str(n) for n in layers)] + \
+    flags = list(extra_flags) + ["-DLGAR_MEASURE", "-DLGAR_LAYERS(X)=" + " ".join("X(%d)" % n for n in layers)] + \
             ([] if tangent else ["-DLGAR_NO_TANGENT"])
     # the stamp covers everything that decides what is in the library: the layer counts and the tangent kernels too (the same
     # name asked for again with other layers must be rebuilt, not returned as it is)

@@ -3,6 +3,8 @@
 // the known-answer tests.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "lgar_geff.hpp"
 #include "lgar_host.hpp"
 #include "lgar_launch.hpp"
@@ -73,57 +75,16 @@ static int check_state(const LgarParams *p, const LgarState *s, const int32_t *s
 
 using namespace lgar;
 
-#ifdef LGAR_ONLY_LAYERS  // measurement variants (build.py build_variant): only these layer counts are linked in
-// (LGAR_ONLY_LAYERS is the layer counts' digits written together, e.g. 3 or 26: a count that is not among them has no
-// translation unit in the library and must not be referred to)
-#define LGAR_HAS_LAYERS(n)                                                                                        \
-  ((LGAR_ONLY_LAYERS) % 10 == n || (LGAR_ONLY_LAYERS) / 10 % 10 == n || (LGAR_ONLY_LAYERS) / 100 % 10 == n ||     \
-   (LGAR_ONLY_LAYERS) / 1000 % 10 == n || (LGAR_ONLY_LAYERS) / 10000 % 10 == n)
-#if LGAR_HAS_LAYERS(2)
-#define LGAR_CASE_2(FN, ...) case 2: return FN<2>(__VA_ARGS__);
-#else
-#define LGAR_CASE_2(FN, ...)
-#endif
-#if LGAR_HAS_LAYERS(3)
-#define LGAR_CASE_3(FN, ...) case 3: return FN<3>(__VA_ARGS__);
-#else
-#define LGAR_CASE_3(FN, ...)
-#endif
-#if LGAR_HAS_LAYERS(4)
-#define LGAR_CASE_4(FN, ...) case 4: return FN<4>(__VA_ARGS__);
-#else
-#define LGAR_CASE_4(FN, ...)
-#endif
-#if LGAR_HAS_LAYERS(5)
-#define LGAR_CASE_5(FN, ...) case 5: return FN<5>(__VA_ARGS__);
-#else
-#define LGAR_CASE_5(FN, ...)
-#endif
-#if LGAR_HAS_LAYERS(6)
-#define LGAR_CASE_6(FN, ...) case 6: return FN<6>(__VA_ARGS__);
-#else
-#define LGAR_CASE_6(FN, ...)
-#endif
-#define LGAR_BY_LAYERS(FN, ...)                        \
-  switch (dims->n_layers) {                            \
-    LGAR_CASE_2(FN, __VA_ARGS__)                       \
-    LGAR_CASE_3(FN, __VA_ARGS__)                       \
-    LGAR_CASE_4(FN, __VA_ARGS__)                       \
-    LGAR_CASE_5(FN, __VA_ARGS__)                       \
-    LGAR_CASE_6(FN, __VA_ARGS__)                       \
-    default: return LGAR_E_ARG;                        \
+// dispatch on the soil-layer count: f(std::integral_constant<int, n>).  A count that is not in LGAR_LAYERS (lgar_plan.hpp;
+// measurement variants link fewer, build.py build_variant) has no translation unit in the library and is a bad argument.
+template <typename F> static int by_layers(int n_layers, F &&f) {
+  switch (n_layers) {
+#define LGAR_X(n) case n: return f(std::integral_constant<int, n>());
+    LGAR_LAYERS(LGAR_X)
+#undef LGAR_X
+    default: return LGAR_E_ARG;
   }
-#else
-#define LGAR_BY_LAYERS(FN, ...)                        \
-  switch (dims->n_layers) {                            \
-    case 2: return FN<2>(__VA_ARGS__);                 \
-    case 3: return FN<3>(__VA_ARGS__);                 \
-    case 4: return FN<4>(__VA_ARGS__);                 \
-    case 5: return FN<5>(__VA_ARGS__);                 \
-    case 6: return FN<6>(__VA_ARGS__);                 \
-    default: return LGAR_E_ARG;                        \
-  }
-#endif
+}
 
 // Basin aggregation of a STORED series (LgarStepOut.basin with series[j] present): basin[t] += sum_c weight[c] series[t][c]
 // (physics/MassBalance.py:77-108 over many columns).  One workgroup per step; every thread sums a fixed strided subset of the
@@ -197,7 +158,9 @@ static void launch_basin_reduce(const void *series, const void *weights, double 
 
 static int forward_by_layers(const LgarDims *dims, const LgarParams *params, LgarState *state, const LgarForcing *forcing,
                              const LgarStepOut *out, int32_t *status, int32_t dtype, hipStream_t stream) {
-  LGAR_BY_LAYERS(launch_forward_nl, dims, params, state, forcing, out, status, dtype, stream)
+  return by_layers(dims->n_layers, [&](auto nl) {
+    return launch_forward_nl<decltype(nl)::value>(dims, params, state, forcing, out, status, dtype, stream);
+  });
 }
 
 extern "C" {
@@ -209,7 +172,7 @@ int32_t lgar_fmax(void) { return LGAR_FMAX; }
 int32_t lgar_lmax(void) { return LGAR_LMAX; }
 int32_t lgar_cooperating_lanes(const LgarDims *dims, int32_t dtype) {
   if (check_dims(dims) != 0 || (dtype != LGAR_F32 && dtype != LGAR_F64)) return LGAR_E_ARG;
-  // (the function forward_typed itself calls, lgar_host.hpp)
+  // (the function forward_plan itself calls, lgar_plan.hpp)
   return dtype == LGAR_F64 ? cooperating_lanes<double>(dims, wave_slots(1)) : cooperating_lanes<float>(dims, wave_slots(1));
 }
 
@@ -219,7 +182,9 @@ int32_t lgar_state_init(const LgarDims *dims, const LgarParams *params, LgarStat
   if (rc) return rc;
   rc = check_state(params, state, status);
   if (rc) return rc;
-  LGAR_BY_LAYERS(launch_init_nl, dims, params, state, status, dtype, (hipStream_t)stream)
+  return by_layers(dims->n_layers, [&](auto nl) {
+    return launch_init_nl<decltype(nl)::value>(dims, params, state, status, dtype, (hipStream_t)stream);
+  });
 }
 
 int32_t lgar_forward(const LgarDims *dims, const LgarParams *params, LgarState *state, const LgarForcing *forcing,
@@ -266,8 +231,10 @@ int32_t lgar_forward_tangent(const LgarDims *dims, const LgarParams *params, con
   if (!params->alpha || !params->n || !params->ksat || !params->theta_e || !params->theta_r || !params->thickness)
     return LGAR_E_ARG;
   if (dims->n_steps > 0 && (!forcing->precip || !forcing->pet)) return LGAR_E_ARG;
-  LGAR_BY_LAYERS(launch_tangent_nl, dims, params, direction, forcing, w_runoff, w_perc, grad_out, tangent_runoff, status,
-                 dtype, (hipStream_t)stream, tickets)
+  return by_layers(dims->n_layers, [&](auto nl) {
+    return launch_tangent_nl<decltype(nl)::value>(dims, params, direction, forcing, w_runoff, w_perc, grad_out, tangent_runoff,
+                                                  status, dtype, (hipStream_t)stream, tickets);
+  });
 }
 #endif
 

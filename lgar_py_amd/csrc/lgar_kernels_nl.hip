@@ -98,40 +98,6 @@ __global__ __launch_bounds__(WAVE, (Occupancy<R, CAP>::waves)) void lgar_forward
   }
 }
 
-template <typename R>
-static KArgs<R> make_args(const LgarDims *d, const LgarParams *p, LgarState *s, const LgarForcing *f, const LgarStepOut *o,
-                          int32_t *status) {
-  KArgs<R> a;
-  a.N = d->n_columns;
-  a.T = d->n_steps;
-  a.F = front_slots(d);
-  a.Nf = forcing_columns(d);
-  a.Fg = forcing_group(d);
-  a.coop = 1;
-  a.ticket = nullptr;
-  a.pending_in = nullptr;
-  a.pending_out = nullptr;
-  a.chain_first = a.chain_last = 1;
-  a.alpha = (const R *)p->alpha; a.n = (const R *)p->n; a.ksat = (const R *)p->ksat;
-  a.theta_e = (const R *)p->theta_e; a.theta_r = (const R *)p->theta_r; a.thick = (const R *)p->thickness;
-  a.depth = (R *)s->depth; a.theta = (R *)s->theta; a.psi = (R *)s->psi; a.k = (R *)s->k; a.dzdt = (R *)s->dzdt;
-  a.flags = s->flags;
-  a.nf = s->n_fronts;
-  a.scalars = (R *)s->scalars;
-  a.totals = (R *)s->totals;
-  a.precip = f ? (const R *)f->precip : nullptr;
-  a.pet = f ? (const R *)f->pet : nullptr;
-  for (int j = 0; j < LGAR_NACC; j++) a.series[j] = o ? (R *)o->series[j] : nullptr;
-  a.basin = o ? o->basin : nullptr;
-  a.basin_mask = o ? o->basin_mask : 0u;
-  a.weights = o ? (const R *)o->weights : nullptr;
-  a.counters = o ? (unsigned long long *)o->counters : nullptr;
-  a.call_sums = o ? (R *)o->call_sums : nullptr;
-  a.status = status;
-  a.G = make_glob<R>(d);
-  return a;
-}
-
 template <typename R, int NL>
 static int init_typed(const LgarDims *dims, const LgarParams *params, LgarState *state, int32_t *status, hipStream_t st) {
   const unsigned grid = (unsigned)((dims->n_columns + WAVE - 1) / WAVE);
@@ -182,48 +148,28 @@ static void launch_fast_kernel(KArgs<R> &a, unsigned nblocks, unsigned *ticket, 
 #endif
 }
 
-// The front-capacity chain of one lgar_forward call (see lgar_forward_body.hpp).
+// One lgar_forward call: the argument block, the plan (lgar_plan.hpp: the front-capacity chain), one launch per kernel of it.
 template <typename R, int NL>
 static int forward_typed(const LgarDims *dims, const LgarParams *params, LgarState *state, const LgarForcing *forcing,
                          const LgarStepOut *out, int32_t *status, hipStream_t st) {
   const unsigned grid = (unsigned)((dims->n_columns + WAVE - 1) / WAVE);
   KArgs<R> a = make_args<R>(dims, params, state, forcing, out, status);
-  const int slots = a.F;
   unsigned *tickets = state->tickets;
   if (tickets != nullptr && hipMemsetAsync(tickets, 0, LGAR_NTICKETS * sizeof(unsigned), st) != hipSuccess) return LGAR_E_LAUNCH;
+  const ForwardPlan plan = forward_plan<R>(dims, NL, wave_slots(1));
+  a.coop = plan.coop;
+  for (int i = 0; i < plan.n; i++) {
+    unsigned *tk = chain_step(a, i, plan.n, tickets);
 #if !(defined(LGAR_MEASURE) && (defined(LGAR_ONLY_MIXED) || defined(LGAR_ONLY_F32)))
-  if (dims->search_mode == 0) {
-    // the reference's literal searches: verification mode, one kernel at the full capacity
-    launch_forward_kernel<R, NL, LGAR_FMAX, MODE_LITERAL>(a, grid, tickets, st);
-    return launch_status();
-  }
+    if (plan.literal) {
+      launch_forward_kernel<R, NL, LGAR_FMAX, MODE_LITERAL>(a, grid, tk, st);
+      return launch_status();
+    }
 #endif
-  // smallest capacity that leaves room for a forcing step (one front per layer + one new front per sub-step + slack);
-  // small jobs (under one wave per SIMD) gain nothing from occupancy and start at the full capacity
-  const int need = NL + dims->num_subcycles + 2;
-  // Jobs that cannot fill the chip (the reference's own use is ONE column, agents/DifferentiableLGAR.py:117-125): in double
-  // precision every column gets 4..64 cooperating lanes that split the Geff trapezoid's nodes, the pows that open it and the
-  // front sweep's independent evaluations (lgar_geff.hpp geff_nodes_cooperative / geff_ends_cooperative, lgar_column.hpp coop_sweep_thetas /
-  // calc_dzdt_pairs).  Results are bit for bit those of one lane per column.  Such a job runs the 32-front kernel directly
-  // (MODE_COOP: front table and exchange table once per GROUP of lanes, 34 KB of LDS per wave, one wave per SIMD): no capacity
-  // chain, no hand-over.
-  a.coop = cooperating_lanes<R>(dims, wave_slots(1));
-  const bool tiny = (grid <= 1024u && dims->search_mode != 2) || a.coop > 1;  // search_mode 2: chain forced (tests)
-  int caps[3], nc = 0;
-  if (!tiny && need <= LGAR_CAP_SMALL && slots > LGAR_CAP_SMALL) caps[nc++] = LGAR_CAP_SMALL;
-  if (!tiny && need <= LGAR_CAP_MID && slots > LGAR_CAP_MID) caps[nc++] = LGAR_CAP_MID;
-  caps[nc++] = LGAR_FMAX;
-  for (int i = 0; i < nc; i++) {
-    a.chain_first = (i == 0);
-    a.chain_last = (i == nc - 1);
-    unsigned *tk = tickets ? tickets + i : nullptr;
-    a.pending_in = (tickets && i > 0) ? tickets + 4 + (i - 1) : nullptr;   // tickets[4..5]: columns handed over by kernel 0, 1
-    a.pending_out = (tickets && i < nc - 1) ? tickets + 4 + i : nullptr;
-    const bool mixed = dims->geff_mode == 1;
-    switch (caps[i]) {
-      case LGAR_CAP_SMALL: launch_fast_kernel<R, NL, LGAR_CAP_SMALL>(a, grid, tk, st, mixed); break;
-      case LGAR_CAP_MID: launch_fast_kernel<R, NL, LGAR_CAP_MID>(a, grid, tk, st, mixed); break;
-      default: launch_fast_kernel<R, NL, LGAR_FMAX>(a, grid, tk, st, mixed); break;
+    switch (plan.caps[i]) {
+      case LGAR_CAP_SMALL: launch_fast_kernel<R, NL, LGAR_CAP_SMALL>(a, grid, tk, st, plan.mixed); break;
+      case LGAR_CAP_MID: launch_fast_kernel<R, NL, LGAR_CAP_MID>(a, grid, tk, st, plan.mixed); break;
+      default: launch_fast_kernel<R, NL, LGAR_FMAX>(a, grid, tk, st, plan.mixed); break;
     }
     const int rc = launch_status();
     if (rc) return rc;
@@ -247,8 +193,9 @@ int launch_forward_nl(const LgarDims *dims, const LgarParams *params, LgarState 
   return LGAR_E_ARG;
 }
 
-#ifdef LGAR_MEASURE
-// measurement builds: read (and zero) the debug counters of this translation unit (lgar_measure.hpp)
+#if defined(LGAR_MEASURE) && defined(LGAR_COUNT_GEFFM_REGIONS)
+// measurement builds that count: read (and zero) the debug counters of this translation unit (lgar_measure.hpp).  Like the
+// clocks below it exists once per layer count's unit, so only in the one-layer-count builds that use it (build.py build_variant)
 extern "C" int lgar_debug_counters(unsigned long long *out, int reset) {
   unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(lgar_dbg_counters), sizeof(z)) != hipSuccess) return -1;

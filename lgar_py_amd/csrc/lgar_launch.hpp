@@ -2,12 +2,12 @@
 //
 // The column physics is templated on the number of layers (per-layer parameters live in registers, loops over layers are
 // unrolled), so each layer count is its own translation unit: lgar_kernels_nl.hip / lgar_tangent_nl.hip are compiled once
-// per NL in LGAR_LMIN..LGAR_LMAX with -DLGAR_NL=<n> (lgar_py_amd/build.py), concurrently.  lgar_kernels.hip holds the
+// per NL of LGAR_LAYERS (lgar_plan.hpp) with -DLGAR_NL=<n> (lgar_py_amd/build.py), concurrently.  lgar_kernels.hip holds the
 // C-ABI and dispatches on dims->n_layers.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "../../include/lgar.h"
+#include "lgar_plan.hpp"  // LGAR_LAYERS
 
 namespace lgar {
 
@@ -25,11 +25,7 @@ template <int NL> int launch_tangent_nl(const LgarDims *, const LgarParams *, co
                                             const LgarStepOut *, int32_t *, int, hipStream_t);                                 \
   extern template int launch_tangent_nl<NL>(const LgarDims *, const LgarParams *, const LgarParams *, const LgarForcing *,     \
                                             const void *, const void *, void *, void *, int32_t *, int, hipStream_t, unsigned *);
-LGAR_DECLARE_NL(2)
-LGAR_DECLARE_NL(3)
-LGAR_DECLARE_NL(4)
-LGAR_DECLARE_NL(5)
-LGAR_DECLARE_NL(6)
+LGAR_LAYERS(LGAR_DECLARE_NL)
 #undef LGAR_DECLARE_NL
 
 }  // namespace lgar

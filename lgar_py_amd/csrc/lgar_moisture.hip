@@ -7,6 +7,7 @@
 // LGAR_MOIST_BINS (the accumulators of the unused bins cost registers, nothing else).
 #include <hip/hip_runtime.h>
 
+#include "lgar_host.hpp"
 #include "lgar_moisture.hpp"
 
 namespace lgar {
@@ -41,7 +42,7 @@ static int launch_typed(const LgarDims *dims, const LgarParams *params, const Lg
   a.out = (R *)out;
   a.N = dims->n_columns;
   a.n_layers = dims->n_layers;
-  a.front_slots = dims->front_slots > 0 ? dims->front_slots : LGAR_FMAX;
+  a.front_slots = front_slots(dims);
   a.n_bins = n_bins;
   a.what = what;
   const dim3 grid((unsigned)(((size_t)dims->n_columns + 255u) / 256u)), block(256);
@@ -49,7 +50,7 @@ static int launch_typed(const LgarDims *dims, const LgarParams *params, const Lg
   else if (n_bins <= 8) hipLaunchKernelGGL((lgar_moisture_kernel<R, 8, false>), grid, block, 0, stream, a);
   else if (n_bins <= 16) hipLaunchKernelGGL((lgar_moisture_kernel<R, 16, false>), grid, block, 0, stream, a);
   else hipLaunchKernelGGL((lgar_moisture_kernel<R, LGAR_MOIST_BINS, false>), grid, block, 0, stream, a);
-  return hipGetLastError() == hipSuccess ? 0 : LGAR_E_LAUNCH;
+  return launch_status();
 }
 
 // one lane per column; rows are lane-contiguous.  The adds are the forward kernels' own (tot = tot + acc, in R, step by step)
@@ -81,7 +82,7 @@ static int replay_typed(const LgarDims *dims, const LgarStepOut *stored, int n_r
   a.N = dims->n_columns;
   a.n_rows = n_rows;
   hipLaunchKernelGGL(lgar_totals_replay_kernel<R>, dim3((unsigned)(((size_t)dims->n_columns + 255u) / 256u)), dim3(256), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? 0 : LGAR_E_LAUNCH;
+  return launch_status();
 }
 
 int launch_totals_replay(const LgarDims *dims, const LgarStepOut *stored, int n_rows, void *running, int dtype, hipStream_t stream) {

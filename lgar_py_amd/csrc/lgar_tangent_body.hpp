@@ -11,7 +11,7 @@
 // those columns again from their fresh state (a tangent run always starts from set_internal_states).
 #pragma once
 #include "lgar_dual.hpp"
-#include "lgar_forward_body.hpp"
+#include "lgar_plan.hpp"
 
 namespace lgar {
 
@@ -32,6 +32,35 @@ template <typename R> struct TArgs {
   int32_t *status;                                        // [N]
   Glob<R> G;
 };
+
+// the argument block of one lgar_forward_tangent call: one kernel on its own, no work counter (as make_args, lgar_plan.hpp)
+template <typename R>
+inline TArgs<R> make_targs(const LgarDims *d, const LgarParams *p, const LgarParams *dir, const LgarForcing *f, const void *w_runoff,
+                           const void *w_perc, void *grad_out, void *tangent_runoff, int32_t *status) {
+  TArgs<R> a;
+  a.N = d->n_columns;
+  a.T = d->n_steps;
+  a.Nf = forcing_columns(d);
+  a.Fg = forcing_group(d);
+  a.share = d->tangent_share;
+  a.F = front_slots(d);
+  a.ticket = nullptr;
+  a.pending_in = nullptr;
+  a.pending_out = nullptr;
+  a.chain_first = a.chain_last = 1;
+  a.alpha = (const R *)p->alpha; a.n = (const R *)p->n; a.ksat = (const R *)p->ksat;
+  a.theta_e = (const R *)p->theta_e; a.theta_r = (const R *)p->theta_r; a.thick = (const R *)p->thickness;
+  a.d_alpha = (const R *)dir->alpha; a.d_n = (const R *)dir->n; a.d_ksat = (const R *)dir->ksat;
+  a.precip = (const R *)f->precip;
+  a.pet = (const R *)f->pet;
+  a.w_runoff = (const R *)w_runoff;
+  a.w_perc = (const R *)w_perc;
+  a.grad_out = (R *)grad_out;
+  a.tangent_runoff = (R *)tangent_runoff;
+  a.status = status;
+  a.G = make_glob<R>(d);
+  return a;
+}
 
 template <typename R, int NL, int FMAX, int MODE>
 __device__ __forceinline__ void tangent_lane(const LGAR_KARG TArgs<R> *ap, size_t c, int lane, WaveLDS<Dual<R>, FMAX, 1> &lds,

@@ -12,8 +12,6 @@
 
 namespace lgar {
 
-__host__ __device__ inline unsigned columns_per_block(int share) { return share >= 2 ? (unsigned)((WAVE / share) * share) : (unsigned)WAVE; }
-
 // Waves per SIMD the register allocator is held to.  The 8-front fp32 kernel needs 259 registers on its own -- three too many
 // for two waves -- and a single resident wave gets an issue slot only every ~7 cycles: held to 256, it
 // runs two waves per SIMD (backward pass of the 100 000-column ensemble 61.6 -> 44.7 ms).  The fp64 kernels stay at one wave:
@@ -71,36 +69,23 @@ static void launch_one(TArgs<R> &a, unsigned nblocks, unsigned *ticket, hipStrea
   hipLaunchKernelGGL((lgar_tangent_kernel<R, NL, CAP, MODE>), dim3(grid), dim3(WAVE), 0, st, a);
 }
 
+// One lgar_forward_tangent call: the argument block, the plan (lgar_plan.hpp), one launch per kernel of it.
 template <typename R, int NL>
 static int tangent_typed(const LgarDims *dims, const LgarParams *params, const LgarParams *direction, const LgarForcing *forcing,
                          const void *w_runoff, const void *w_perc, void *grad_out, void *tangent_runoff, int32_t *status,
                          hipStream_t st, unsigned *tickets) {
-  const unsigned cpb = columns_per_block(dims->tangent_share);
-  const unsigned nblocks = ((unsigned)dims->n_columns + cpb - 1) / cpb;
   if (tickets != nullptr && hipMemsetAsync(tickets, 0, LGAR_NTICKETS * sizeof(unsigned), st) != hipSuccess) return LGAR_E_LAUNCH;
-  TArgs<R> a{dims->n_columns, dims->n_steps, forcing_columns(dims), forcing_group(dims), dims->tangent_share, front_slots(dims),
-             nullptr, nullptr, nullptr, 1, 1, (const R *)params->alpha, (const R *)params->n, (const R *)params->ksat,
-             (const R *)params->theta_e, (const R *)params->theta_r, (const R *)params->thickness,
-             (const R *)direction->alpha, (const R *)direction->n, (const R *)direction->ksat,
-             (const R *)forcing->precip, (const R *)forcing->pet, (const R *)w_runoff, (const R *)w_perc,
-             (R *)grad_out, (R *)tangent_runoff, status, make_glob<R>(dims)};
-  if (dims->search_mode == 0) {
-    launch_one<R, NL, LGAR_FMAX, MODE_LITERAL>(a, nblocks, tickets, st);
-    return launch_status();
-  }
-  const bool chain = (NL + dims->num_subcycles + 2 <= LGAR_CAP_SMALL) && (nblocks > 1024u || dims->search_mode == 2);
-  if (chain) {
-    a.chain_first = 1; a.chain_last = 0;
-    a.pending_out = tickets ? tickets + 4 : nullptr;
-    launch_one<R, NL, LGAR_CAP_SMALL, MODE_FAST>(a, nblocks, tickets, st);
-    int rc = launch_status();
+  TArgs<R> a = make_targs<R>(dims, params, direction, forcing, w_runoff, w_perc, grad_out, tangent_runoff, status);
+  const TangentPlan plan = tangent_plan(dims, NL);
+  for (int i = 0; i < plan.n; i++) {
+    unsigned *tk = chain_step(a, i, plan.n, tickets);
+    if (plan.literal) launch_one<R, NL, LGAR_FMAX, MODE_LITERAL>(a, plan.blocks, tk, st);
+    else if (plan.caps[i] == LGAR_CAP_SMALL) launch_one<R, NL, LGAR_CAP_SMALL, MODE_FAST>(a, plan.blocks, tk, st);
+    else launch_one<R, NL, LGAR_FMAX, MODE_FAST>(a, plan.blocks, tk, st);
+    const int rc = launch_status();
     if (rc) return rc;
-    a.chain_first = 0; a.chain_last = 1;
-    a.pending_in = a.pending_out;
-    a.pending_out = nullptr;
   }
-  launch_one<R, NL, LGAR_FMAX, MODE_FAST>(a, nblocks, tickets ? tickets + 1 : nullptr, st);
-  return launch_status();
+  return 0;
 }
 
 template <int NL>

@@ -87,22 +87,10 @@ class LgarEngine:
         if not (float(dt_h) > 0 and int(num_subcycles) >= 1 and int(nint) >= 1 and float(initial_psi) > 0):
             raise LgarError("need dt_h > 0, num_subcycles >= 1, nint >= 1, initial_psi > 0")
         self.L, self.N = L, N
-        self.dims = _capi.LgarDims()
-        d = self.dims
-        d.n_columns, d.n_layers, d.n_steps, d.num_subcycles = N, L, 0, int(num_subcycles)
-        d.nint, d.n_giuh, d.search_mode = int(nint), len(giuh_ordinates), int(search_mode)
-        d.dt_h, d.initial_psi, d.ponded_depth_max = float(dt_h), float(initial_psi), float(ponded_depth_max)
-        d.wilting_point_psi, d.frozen_factor = float(wilting_point_psi), float(frozen_factor)
-        for i, g in enumerate(giuh_ordinates):
-            d.giuh[i] = float(g)
-        d.iter_cap = int(iter_cap)
-        d.bottom_mode = int(bottom_mode)
-        d.use_closed_form_G = int(bool(use_closed_form_G))
         if geff_precision not in ("native", "f32"):
             raise LgarError("geff_precision must be 'native' or 'f32'")
         if geff_precision == "f32" and (dtype != torch.float64 or int(search_mode) == 0):
             raise LgarError("geff_precision='f32' is the mixed mode of the fp64 fast searches (dtype float64, search_mode 1 or 2)")
-        d.geff_mode = 1 if geff_precision == "f32" else 0
         self.geff_precision = geff_precision
         forward_lanes = int(forward_lanes)
         if forward_lanes not in (0, 1) and not 4 <= forward_lanes <= 64:
@@ -110,13 +98,17 @@ class LgarEngine:
         if forward_lanes > 1 and (dtype != torch.float64 or int(search_mode) == 0 or use_closed_form_G or int(nint) > 128):
             raise LgarError("forward_lanes=%d cannot be honoured: cooperating lanes exist for the fp64 fast modes (native or "
                             "mixed-precision trapezoid; no closed-form G, nint <= 128) only" % forward_lanes)
-        d.forward_lanes = forward_lanes
         self.basin_scratch_bytes = int(basin_scratch_bytes)
         FMAX = int(front_slots) if front_slots else _capi.FMAX
         if not L + 1 <= FMAX <= _capi.FMAX:
             raise LgarError("front_slots must be in %d..%d" % (L + 1, _capi.FMAX))
-        d.front_slots = FMAX
         self.front_slots = FMAX
+        self.dims = _capi.make_dims(
+            n_columns=N, n_layers=L, dt_h=dt_h, num_subcycles=num_subcycles, initial_psi=initial_psi,
+            ponded_depth_max=ponded_depth_max, wilting_point_psi=wilting_point_psi, frozen_factor=frozen_factor, nint=nint,
+            giuh_ordinates=giuh_ordinates, iter_cap=iter_cap, search_mode=search_mode, bottom_mode=bottom_mode,
+            use_closed_form_G=use_closed_form_G, front_slots=FMAX, geff_mode=1 if geff_precision == "f32" else 0,
+            forward_lanes=forward_lanes)
 
         self.status = torch.zeros(N, dtype=torch.int32, device=self.device)
         if not with_state:  # tangent-only engine (autograd.parameter_vjp): the tangent kernels keep no state in HBM

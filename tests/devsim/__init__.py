@@ -5,77 +5,48 @@ for the host with -DLGAR_DEVSIM, one lane at a time.  CPU tests use it to run th
 reference's golden vectors.  Never imported by the product package; never timed.
 """
 import ctypes as C
+import hashlib
 import os
 import subprocess
+import threading
 
 import numpy as np
 
+import _hostbuild
+from _hostbuild import CLANG, CSRC, ROOT  # noqa: F401
+# the one mirror of include/lgar.h (tests/test_capi_host.py checks it against the header)
+from lgar_py_amd._capi import (ACC_NAMES, FMAX, GMAX, NACC, NCOUNTERS, NSCAL, LgarDims, LgarForcing, LgarParams,  # noqa: F401
+                               LgarState, LgarStepOut, make_dims)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(_HERE))
-CSRC = os.path.join(ROOT, "lgar_py_amd", "csrc")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
-FMAX, GMAX, NACC, NSCAL, NCOUNTERS = 32, 8, 10, 11, 4
-ACC_NAMES = ["precip", "PET", "AET", "infiltration", "runoff", "percolation", "giuh_runoff", "discharge",
-             "ponded_water", "ending_volume"]
-
-
-class LgarDims(C.Structure):
-    _fields_ = [("n_columns", C.c_int32), ("n_layers", C.c_int32), ("n_steps", C.c_int32),
-                ("num_subcycles", C.c_int32), ("nint", C.c_int32), ("n_giuh", C.c_int32),
-                ("search_mode", C.c_int32), ("bottom_mode", C.c_int32), ("use_closed_form_G", C.c_int32), ("front_slots", C.c_int32),
-                ("dt_h", C.c_double), ("initial_psi", C.c_double), ("ponded_depth_max", C.c_double),
-                ("wilting_point_psi", C.c_double), ("frozen_factor", C.c_double), ("giuh", C.c_double * GMAX),
-                ("iter_cap", C.c_int64), ("forcing_columns", C.c_int32), ("forcing_group", C.c_int32),
-                ("tangent_share", C.c_int32), ("geff_mode", C.c_int32), ("forward_lanes", C.c_int32), ("reserved4", C.c_int32)]
-
-
-class LgarParams(C.Structure):
-    _fields_ = [(nm, C.c_void_p) for nm in ("alpha", "n", "ksat", "theta_e", "theta_r", "thickness")]
-
-
-class LgarState(C.Structure):
-    _fields_ = [(nm, C.c_void_p) for nm in ("depth", "theta", "psi", "k", "dzdt", "flags", "n_fronts", "scalars", "totals", "tickets")]
-
-
-class LgarForcing(C.Structure):
-    _fields_ = [("precip", C.c_void_p), ("pet", C.c_void_p)]
-
-
-class LgarStepOut(C.Structure):
-    _fields_ = [("series", C.c_void_p * NACC), ("basin", C.c_void_p), ("weights", C.c_void_p), ("basin_mask", C.c_uint32),
-                ("reserved", C.c_uint32), ("counters", C.c_void_p), ("call_sums", C.c_void_p)]
-
-
 _libs = {}
+_lock = threading.Lock()
 
 
-def lib(n_layers):
-    """libdevsim_<L>.so, built on first use (one soil-layer count per library keeps each build under a minute)."""
-    if n_layers in _libs:
-        return _libs[n_layers]
+def lib(n_layers, flags=(), sanitize=None):
+    """libdevsim_<L>.so, built on first use (one soil-layer count per library keeps each build under a minute).  flags: extra
+    compiler flags (a tuple of -D... strings: tests/devsim/variants.py) -> libdevsim_v<tag>_<L>.so."""
     # DEVSIM_SANITIZE=1: the AddressSanitizer + UBSan build (the process must run under LD_PRELOAD of clang's asan runtime:
     # tests/test_sanitizers.py)
-    san = os.environ.get("DEVSIM_SANITIZE") == "1"
-    so = os.path.join(_HERE, "libdevsim_%s%d.so" % ("san_" if san else "", n_layers))
-    deps = [os.path.join(_HERE, "devsim.cpp"), os.path.join(ROOT, "include", "lgar.h")] + \
-           [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        if not os.path.exists(CLANG):
-            raise RuntimeError("clang++ of the ROCm toolchain not found: cannot build the device-code simulator")
-        tmp = "%s.%d.tmp" % (so, os.getpid())  # (several test workers may build the same library at once)
-        # (the sanitizer build at -O0: a minute instead of six at -O1; its fixtures run in a second either way)
-        extra = ["-O0", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-shared-libsan"] if san else []
-        subprocess.check_call([CLANG, "-x", "c++", "-std=c++17", "-O1", "-ffp-contract=off", "-fPIC", "-shared"] + extra +
-                              ["-I", os.path.join(ROOT, "include"), "-DDEVSIM_LAYERS(X)=X(%d)" % n_layers,
-                               os.path.join(_HERE, "devsim.cpp"), "-o", tmp])
-        os.replace(tmp, so)
+    san = os.environ.get("DEVSIM_SANITIZE") == "1" if sanitize is None else bool(sanitize)
+    key = (n_layers, tuple(flags), san)
+    with _lock:
+        if key in _libs:
+            return _libs[key]
+    # (compiles run outside the lock: prebuild() runs several at once)
+    tag = ("san_" if san else "") + ("v%s_" % hashlib.sha256(" ".join(flags).encode()).hexdigest()[:10] if flags else "")
+    # (the sanitizer build at -O0: a minute instead of six at -O1; its fixtures run in a second either way)
+    extra = ["-O0"] + _hostbuild.SANITIZE + ["-shared-libsan"] if san else []
+    so = _hostbuild.build(os.path.join(_HERE, "libdevsim_%s%d.so" % (tag, n_layers)), os.path.join(_HERE, "devsim.cpp"),
+                          _hostbuild.device_headers(), ["-fPIC", "-shared"] + extra + list(flags) + ["-DLGAR_LAYERS(X)=X(%d)" % n_layers],
+                          "the device-code simulator")
     L = C.CDLL(so)
     p, i32, vp = C.POINTER, C.c_int32, C.c_void_p
     L.devsim_state_init.argtypes = [p(LgarDims), p(LgarParams), p(LgarState), vp, i32]
     L.devsim_forward.argtypes = [p(LgarDims), p(LgarParams), p(LgarState), p(LgarForcing), p(LgarStepOut), vp, i32]
     L.devsim_tangent.argtypes = [p(LgarDims), p(LgarParams), p(LgarParams), p(LgarForcing), vp, vp, vp, vp, vp, i32]
-    _libs[n_layers] = L
-    return L
+    with _lock:
+        return _libs.setdefault(key, L)
 
 
 def sanitizer_runtime():
@@ -112,17 +83,12 @@ class SimEngine:
         L, N = self.alpha.shape
         self.L, self.N = L, N
         self.lib = lib(L)
-        d = self.dims = LgarDims()
-        d.n_columns, d.n_layers, d.n_steps, d.num_subcycles = N, L, 0, int(num_subcycles)
-        d.nint, d.n_giuh, d.search_mode = int(nint), len(giuh_ordinates), int(search_mode)
-        d.dt_h, d.initial_psi, d.ponded_depth_max = float(dt_h), float(initial_psi), float(ponded_depth_max)
-        d.wilting_point_psi, d.frozen_factor = float(wilting_point_psi), float(frozen_factor)
-        for i, g in enumerate(giuh_ordinates):
-            d.giuh[i] = float(g)
-        d.iter_cap, d.bottom_mode, d.use_closed_form_G = int(iter_cap), int(bottom_mode), int(bool(use_closed_form_G))
-        d.geff_mode = int(geff_mode)
-        F = int(front_slots) if front_slots else FMAX
-        d.front_slots = F
+        d = self.dims = make_dims(
+            n_columns=N, n_layers=L, dt_h=dt_h, num_subcycles=num_subcycles, initial_psi=initial_psi,
+            ponded_depth_max=ponded_depth_max, wilting_point_psi=wilting_point_psi, frozen_factor=frozen_factor, nint=nint,
+            giuh_ordinates=giuh_ordinates, iter_cap=iter_cap, search_mode=search_mode, bottom_mode=bottom_mode,
+            use_closed_form_G=use_closed_form_G, front_slots=front_slots, geff_mode=geff_mode)
+        F = d.front_slots
         z = lambda *s, dt=self.dtype: np.zeros(s, dtype=dt)
         self.depth, self.theta, self.psi, self.k, self.dzdt = z(F, N), z(F, N), z(F, N), z(F, N), z(F, N)
         self.flags, self.n_fronts = z(F, N, dt=np.uint8), z(N, dt=np.int32)

@@ -9,10 +9,10 @@ import tempfile
 
 import numpy as np
 
+import _hostbuild
+from _hostbuild import CSRC, ROOT
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(_HERE))
-CSRC = os.path.join(ROOT, "lgar_py_amd", "csrc")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 WHAT = {"theta": 0, "storage": 1}
 
 
@@ -65,16 +65,10 @@ def same_bits(a, b):
 
 def program(sanitize=False):
     """The host program, built on first use with the ROCm clang (sanitize: AddressSanitizer + UBSan, any finding aborts)."""
-    exe = os.path.join(_HERE, "moisture_host_san" if sanitize else "moisture_host")
-    deps = [os.path.join(_HERE, "moisture_host.cpp"), os.path.join(CSRC, "lgar_moisture.hpp"), os.path.join(ROOT, "include", "lgar.h")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        if not os.path.exists(CLANG):
-            raise RuntimeError("clang++ of the ROCm toolchain not found: cannot build the soil-moisture host program")
-        tmp = "%s.%d.tmp" % (exe, os.getpid())
-        extra = ["-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else []
-        subprocess.check_call([CLANG, "-x", "c++", "-std=c++17", "-O1", "-ffp-contract=off"] + extra + [deps[0], "-o", tmp])
-        os.replace(tmp, exe)
-    return exe
+    return _hostbuild.build(os.path.join(_HERE, "moisture_host_san" if sanitize else "moisture_host"),
+                            os.path.join(_HERE, "moisture_host.cpp"),
+                            [os.path.join(CSRC, "lgar_moisture.hpp"), os.path.join(ROOT, "include", "lgar.h")],
+                            _hostbuild.SANITIZE if sanitize else [], "the soil-moisture host program")
 
 
 def run_cases(cases, sanitize=False):

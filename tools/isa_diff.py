@@ -1,7 +1,7 @@
 """Which kernels did a change touch?  Compiles lgar_kernels_nl.hip (3 soil layers, the product flags) from the working tree and
 from a git revision, disassembles both code objects and compares every kernel instruction by instruction (branch targets and
 literal addresses aside).  A kernel reported SAME executes the very instruction stream it did at that revision: its parity
-sweeps, counters and timings carry over.  Runs where hipcc is (no GPU needed).  usage: python tools/isa_diff.py [REV=HEAD] [UNIT]
+sweeps, counters and timings carry over.  Runs where hipcc is (no GPU needed).  usage: python tools/isa_diff.py [REV=HEAD] [UNIT] [LAYERS=3]
 (dev tool)"""
 import os
 import re
@@ -16,7 +16,7 @@ from lgar_py_amd import build as B
 LLVM = "/opt/rocm/lib/llvm/bin"
 rev = sys.argv[1] if len(sys.argv) > 1 else "HEAD"
 unit = sys.argv[2] if len(sys.argv) > 2 else "lgar_kernels_nl.hip"
-flags = [f for f in B.FLAGS if f != "-shared"] + ["-DLGAR_NL=3"]
+flags = [f for f in B.FLAGS if f != "-shared"] + ["-DLGAR_NL=%d" % (int(sys.argv[3]) if len(sys.argv) > 3 else 3)]
 
 
 def kernels(src_root, tag, tmp):
