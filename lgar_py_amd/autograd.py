@@ -59,13 +59,8 @@ def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True):
         # column n's Dg directions sit in ADJACENT lanes (column n * Dg + b): they follow the same branches, so a wavefront
         # diverges over 64 / Dg columns instead of 64; the kernel reads forcing / weight column c // Dg (forcing_group)
         rep = lambda t: t.repeat_interleave(Dg, dim=1)
-        big = LgarEngine(rep(eng.alpha), rep(eng.n), rep(eng.ksat), rep(eng.theta_e), rep(eng.theta_r), rep(eng.thickness),
-                         dt_h=d.dt_h, num_subcycles=d.num_subcycles, initial_psi=d.initial_psi,
-                         ponded_depth_max=d.ponded_depth_max, wilting_point_psi=d.wilting_point_psi,
-                         frozen_factor=d.frozen_factor, nint=d.nint, giuh_ordinates=tuple(d.giuh[i] for i in range(d.n_giuh)),
-                         dtype=eng.dtype, device=eng.device, iter_cap=d.iter_cap, search_mode=d.search_mode,
-                         bottom_mode=d.bottom_mode, use_closed_form_G=bool(d.use_closed_form_G), front_slots=eng.front_slots,
-                         with_state=False)
+        big = eng.like(rep(eng.alpha), rep(eng.n), rep(eng.ksat), rep(eng.theta_e), rep(eng.theta_r), rep(eng.thickness),
+                       with_state=False)
         dirs = {k: torch.zeros(L, Dg * N, dtype=eng.dtype, device=eng.device) for k in KINDS}
         for b, (kind, l) in enumerate(part):
             dirs[kind][l, b::Dg] = 1.0

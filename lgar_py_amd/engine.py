@@ -12,11 +12,24 @@ from . import _capi
 from ._capi import ACC_NAMES, GMAX, LMAX, LMIN, NACC, NSCAL, LgarError
 
 BASIN_SCRATCH_BYTES = 8 << 30  # most series memory, over ALL basin names, an engine allocates on its own behind basin sums
+PARAMS = ("alpha", "n", "ksat", "theta_e", "theta_r", "thickness")
+# LgarEngine's keyword settings and their defaults (the class docstring says what they mean); an engine keeps the ones it
+# was built with in `settings`
+SETTINGS = dict(dt_h=1.0, num_subcycles=1, initial_psi=2000.0, ponded_depth_max=0.0, wilting_point_psi=15495.0,
+                frozen_factor=1.0, nint=120, giuh_ordinates=(0.06, 0.51, 0.28, 0.12, 0.03), dtype=torch.float64,
+                device="cuda:0", iter_cap=0, search_mode=1, bottom_mode=0, use_closed_form_G=False, front_slots=None,
+                geff_precision="native", forward_lanes=0, basin_scratch_bytes=BASIN_SCRATCH_BYTES)
+_DIMS_SETTINGS = ("dt_h", "num_subcycles", "initial_psi", "ponded_depth_max", "wilting_point_psi", "frozen_factor", "nint",
+                  "giuh_ordinates", "iter_cap", "search_mode", "bottom_mode", "use_closed_form_G", "forward_lanes")
 
 
 def _require_gpu(device):
     if not torch.cuda.is_available():
         raise LgarError("no ROCm GPU visible: the LGAR engine has no CPU fallback (device=%s)" % (device,))
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
 
 
 class LgarStatusError(ValueError):
@@ -26,7 +39,8 @@ class LgarStatusError(ValueError):
 class LgarEngine:
     """N independent soil columns advanced by the gfx950 kernels.
 
-    Parameters are [L] (shared by all columns) or [L, N] tensors/sequences; forcing is [T, N] (cm/h).
+    Parameters are [L] (shared by all columns) or [L, N] tensors/sequences; forcing is [T, N] (cm/h).  The other arguments
+    are keywords (SETTINGS has the defaults):
     search_mode: 1 (default) = bracketed-Newton psi search + closed-form jumps in the depth search (same roots, same
     tolerances); 0 = verification mode: the reference's literal fixed-step line searches (Layer.py:275-317, 681-701),
     its update_psi pass and, in fp64, its trapezoid operation by operation; 2 = like 1 with the front-capacity chain
@@ -45,16 +59,24 @@ class LgarEngine:
     did not ask for (see forward); 0 = never, such sums are taken by the in-kernel atomics instead.
     bottom_mode: 0 (default) = like the reference, a front reaching the domain bottom faults the column; 1 = it leaves
     the column as percolation (LGAR-C intent; parity unpinned, the reference crashes there).
+    with_state=False: a tangent-only engine (autograd.parameter_vjp): the tangent kernels keep no state in HBM.
+
+    What is about the library behind the calling surface sits in _open, _call, step_rows_host and cooperating_lanes; the
+    test suite's device-code simulator replaces those and runs everything else of this class on the CPU.
     """
 
-    def __init__(self, alpha, n, ksat, theta_e, theta_r, thickness, *, n_columns=None, dt_h=1.0, num_subcycles=1,
-                 initial_psi=2000.0, ponded_depth_max=0.0, wilting_point_psi=15495.0, frozen_factor=1.0, nint=120,
-                 giuh_ordinates=(0.06, 0.51, 0.28, 0.12, 0.03), dtype=torch.float64, device="cuda:0",
-                 iter_cap=0, search_mode=1, bottom_mode=0, use_closed_form_G=False, front_slots=None, with_state=True,
-                 geff_precision="native", forward_lanes=0, basin_scratch_bytes=BASIN_SCRATCH_BYTES):
-        self.device = torch.device(device)
-        _require_gpu(self.device)
-        self.lib = _capi.load()
+    _new_series = staticmethod(torch.empty)  # (rows of a column that faulted before them are never written)
+
+    def __init__(self, alpha, n, ksat, theta_e, theta_r, thickness, *, n_columns=None, with_state=True, **settings):
+        unknown = sorted(set(settings) - set(SETTINGS))
+        if unknown:
+            raise TypeError("LgarEngine got unexpected keyword arguments %s" % ", ".join(unknown))
+        s = self.settings = dict(SETTINGS, **settings)
+        L = len(alpha)
+        if not LMIN <= L <= LMAX:
+            raise LgarError("this build supports %d..%d soil layers (got %d)" % (LMIN, LMAX, L))
+        self.lib, self.device = self._open(L, s["device"])
+        dtype = s["dtype"]
         if dtype not in (torch.float32, torch.float64):
             raise LgarError("dtype must be torch.float32 or torch.float64")
         self.dtype = dtype
@@ -70,13 +92,11 @@ class LgarEngine:
 
         self.alpha, self.n, self.ksat = prep(alpha), prep(n), prep(ksat)
         self.theta_e, self.theta_r, self.thickness = prep(theta_e), prep(theta_r), prep(thickness)
-        L, N = self.alpha.shape
-        if not LMIN <= L <= LMAX:
-            raise LgarError("this build supports %d..%d soil layers (got %d)" % (LMIN, LMAX, L))
+        N = self.alpha.shape[1]
         for t in (self.n, self.ksat, self.theta_e, self.theta_r, self.thickness):
             if tuple(t.shape) != (L, N):
                 raise LgarError("parameter shapes differ: expected %s, got %s" % ((L, N), tuple(t.shape)))
-        if len(giuh_ordinates) > GMAX:
+        if len(s["giuh_ordinates"]) > GMAX:
             raise LgarError("at most %d GIUH ordinates" % GMAX)
         # physical sanity of the soil table (the reference would run into NaNs / negative pow bases much later)
         bad = [nm for nm, ok in (("alpha > 0", self.alpha > 0), ("n > 1", self.n > 1), ("ksat > 0", self.ksat > 0),
@@ -84,37 +104,34 @@ class LgarEngine:
                                  ("thickness > 0", self.thickness > 0)) if not bool(ok.all())]
         if bad:
             raise LgarError("invalid soil parameters: need " + ", ".join(bad))
-        if not (float(dt_h) > 0 and int(num_subcycles) >= 1 and int(nint) >= 1 and float(initial_psi) > 0):
+        nint, search_mode = int(s["nint"]), int(s["search_mode"])
+        if not (float(s["dt_h"]) > 0 and int(s["num_subcycles"]) >= 1 and nint >= 1 and float(s["initial_psi"]) > 0):
             raise LgarError("need dt_h > 0, num_subcycles >= 1, nint >= 1, initial_psi > 0")
         self.L, self.N = L, N
+        geff_precision = s["geff_precision"]
         if geff_precision not in ("native", "f32"):
             raise LgarError("geff_precision must be 'native' or 'f32'")
-        if geff_precision == "f32" and (dtype != torch.float64 or int(search_mode) == 0):
+        if geff_precision == "f32" and (dtype != torch.float64 or search_mode == 0):
             raise LgarError("geff_precision='f32' is the mixed mode of the fp64 fast searches (dtype float64, search_mode 1 or 2)")
         self.geff_precision = geff_precision
-        forward_lanes = int(forward_lanes)
+        forward_lanes = s["forward_lanes"] = int(s["forward_lanes"])
         if forward_lanes not in (0, 1) and not 4 <= forward_lanes <= 64:
             raise LgarError("forward_lanes must be 0 (library's choice), 1, or 4..64 (got %d)" % forward_lanes)
-        if forward_lanes > 1 and (dtype != torch.float64 or int(search_mode) == 0 or use_closed_form_G or int(nint) > 128):
+        if forward_lanes > 1 and (dtype != torch.float64 or search_mode == 0 or s["use_closed_form_G"] or nint > 128):
             raise LgarError("forward_lanes=%d cannot be honoured: cooperating lanes exist for the fp64 fast modes (native or "
                             "mixed-precision trapezoid; no closed-form G, nint <= 128) only" % forward_lanes)
-        self.basin_scratch_bytes = int(basin_scratch_bytes)
-        FMAX = int(front_slots) if front_slots else _capi.FMAX
+        self.basin_scratch_bytes = int(s["basin_scratch_bytes"])
+        FMAX = int(s["front_slots"]) if s["front_slots"] else _capi.FMAX
         if not L + 1 <= FMAX <= _capi.FMAX:
             raise LgarError("front_slots must be in %d..%d" % (L + 1, _capi.FMAX))
         self.front_slots = FMAX
-        self.dims = _capi.make_dims(
-            n_columns=N, n_layers=L, dt_h=dt_h, num_subcycles=num_subcycles, initial_psi=initial_psi,
-            ponded_depth_max=ponded_depth_max, wilting_point_psi=wilting_point_psi, frozen_factor=frozen_factor, nint=nint,
-            giuh_ordinates=giuh_ordinates, iter_cap=iter_cap, search_mode=search_mode, bottom_mode=bottom_mode,
-            use_closed_form_G=use_closed_form_G, front_slots=FMAX, geff_mode=1 if geff_precision == "f32" else 0,
-            forward_lanes=forward_lanes)
+        self.dims = _capi.make_dims(n_columns=N, n_layers=L, front_slots=FMAX, geff_mode=1 if geff_precision == "f32" else 0,
+                                    **{k: s[k] for k in _DIMS_SETTINGS})
 
         self.status = torch.zeros(N, dtype=torch.int32, device=self.device)
-        if not with_state:  # tangent-only engine (autograd.parameter_vjp): the tangent kernels keep no state in HBM
-            self._params = _capi.LgarParams(*[t.data_ptr() for t in (self.alpha, self.n, self.ksat, self.theta_e,
-                                                                     self.theta_r, self.thickness)])
-            self._state = None
+        self._params = _capi.LgarParams(*[getattr(self, nm).data_ptr() for nm in PARAMS])
+        self._state = None
+        if not with_state:
             return
         z = lambda *shape, dt=dtype: torch.zeros(*shape, dtype=dt, device=self.device)
         self.depth, self.theta, self.psi = z(FMAX, N), z(FMAX, N), z(FMAX, N)
@@ -126,38 +143,77 @@ class LgarEngine:
         self.counters = z(_capi.NCOUNTERS, dt=torch.int64)
         self._basin_scratch = (0, {})  # series buffers behind basin sums whose series the caller did not ask for
         self.tickets = z(_capi.NTICKETS, dt=torch.int32)  # work counters of the persistent-wave schedule
-
-        self._params = _capi.LgarParams(*[t.data_ptr() for t in (self.alpha, self.n, self.ksat, self.theta_e,
-                                                                 self.theta_r, self.thickness)])
         self._state = _capi.LgarState(*[t.data_ptr() for t in (self.depth, self.theta, self.psi, self.k, self.dzdt,
                                                                self.flags, self.n_fronts, self.scalars, self.totals,
                                                                self.tickets)])
         self.reset()
 
+    def like(self, alpha, n, ksat, theta_e, theta_r, thickness, with_state=True, **changes):
+        """An engine of this class with this one's settings (and `changes`) over other parameter arrays ([L, N]).
+        with_state=False: the tangent-only sibling, which takes what the tangent kernels have -- the native trapezoid and no
+        cooperating forward lanes."""
+        # (ponded_depth_max as it stands now: the model updates it in dims)
+        kw = dict(self.settings, device=self.device, ponded_depth_max=self.dims.ponded_depth_max, front_slots=self.front_slots)
+        if not with_state:
+            kw.update(geff_precision="native", forward_lanes=0)
+        kw.update(changes)
+        return type(self)(alpha, n, ksat, theta_e, theta_r, thickness, with_state=with_state, **kw)
+
+    # the library behind the calling surface -----------------------------------------------------
+    def _open(self, n_layers, device):
+        """(library, torch.device) this engine runs on."""
+        device = torch.device(device)
+        _require_gpu(device)
+        return _capi.load(), device
+
+    def _call(self, name, *args, counters=None):
+        """Entry point lgar_<name> on this engine's device and current stream: `args`, then the dtype code, the stream and, for
+        the tangent, its work counters."""
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with torch.cuda.device(self.device):
+            rc = getattr(self.lib, "lgar_" + name)(*args, self._dt, stream, *(() if counters is None else (counters.data_ptr(),)))
+        _capi.check(rc, "lgar_" + name)
+
     # ------------------------------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    def _need_state(self):
+        if self._state is None:
+            raise LgarError("this engine was created with with_state=False (tangent launches only)")
 
     def reset(self):
         """dpLGAR.set_internal_states() for every column."""
-        with torch.cuda.device(self.device):
-            rc = self.lib.lgar_state_init(C.byref(self.dims), C.byref(self._params), C.byref(self._state),
-                                          self.status.data_ptr(), self._dt, self._stream())
-        _capi.check(rc, "lgar_state_init")
+        self._call("state_init", C.byref(self.dims), C.byref(self._params), C.byref(self._state), self.status.data_ptr())
 
     def release_scratch(self):
         """Free the series buffers forward() keeps behind basin sums (they come back on the next such call)."""
         self._basin_scratch = (0, {})
 
-    def _set_forcing_layout(self, precip, pet, forcing_group):
+    def _forcing(self, precip, pet, forcing_group):
+        """The forcing pair on the device in the engine's dtype ([T, Nf]; a 1-D pair is one row), checked, with LgarDims'
+        per-call fields (n_steps and the forcing layout) set for it."""
+        precip = torch.as_tensor(precip).to(self.device, self.dtype).contiguous()
+        pet = torch.as_tensor(pet).to(self.device, self.dtype).contiguous()
+        if precip.dim() == 1:
+            precip, pet = precip[None, :], pet[None, :]
         g = max(1, int(forcing_group))
         if (precip.shape != pet.shape or precip.dim() != 2 or precip.shape[1] < 1 or self.N % g != 0
                 or (self.N // g) % precip.shape[1] != 0):
             raise LgarError("forcing must be [T, %d] (or [T, Nf] with forcing_group * Nf dividing it: column c reads forcing "
                             "column (c // forcing_group) %% Nf); got %s / %s, forcing_group %d"
                             % (self.N, tuple(precip.shape), tuple(pet.shape), g))
-        self.dims.forcing_columns = precip.shape[1]
-        self.dims.forcing_group = g
+        d = self.dims
+        d.n_steps, d.forcing_columns, d.forcing_group = precip.shape[0], precip.shape[1], g
+        return precip, pet
+
+    def _step_out(self, series, basin=None, basin_names=(), weights=None, call_sums=None):
+        """LgarStepOut over {name: [T, N] buffer} (+ the basin block with its names and weights, the call sums)."""
+        so = _capi.LgarStepOut()
+        for nm, buf in series.items():
+            so.series[ACC_NAMES.index(nm)] = buf.data_ptr()
+        so.basin, so.weights, so.call_sums = _ptr(basin), _ptr(weights), _ptr(call_sums)
+        for nm in basin_names:
+            so.basin_mask |= 1 << ACC_NAMES.index(nm)
+        so.counters = self.counters.data_ptr()
+        return so
 
     def forward(self, precip, pet, series=("runoff", "percolation"), out=None, check=True, basin=(), weights=None,
                 call_sums=False, forcing_group=1):
@@ -174,58 +230,42 @@ class LgarEngine:
         basin_scratch_bytes (default 8 GiB; 0 = never); past that the sum falls back to the in-kernel atomics and nothing is
         allocated.  release_scratch() frees them.  call_sums=True adds "call_sums": [NACC, N], the accumulators summed over this
         call's steps (rows 8, 9: latest ponded_water / ending_volume)."""
-        if self._state is None:
-            raise LgarError("this engine was created with with_state=False (tangent launches only)")
-        precip = torch.as_tensor(precip).to(self.device, self.dtype).contiguous()
-        pet = torch.as_tensor(pet).to(self.device, self.dtype).contiguous()
-        if precip.dim() == 1:
-            precip, pet = precip[None, :], pet[None, :]
-        self._set_forcing_layout(precip, pet, forcing_group)
+        self._need_state()
+        precip, pet = self._forcing(precip, pet, forcing_group)
         T = precip.shape[0]
         res = {}
-        so = _capi.LgarStepOut()
         for nm in series:
-            j = ACC_NAMES.index(nm)
-            buf = out[nm] if out is not None and nm in out else torch.empty(T, self.N, dtype=self.dtype, device=self.device)
+            buf = out[nm] if out is not None and nm in out else self._new_series(T, self.N, dtype=self.dtype, device=self.device)
             if tuple(buf.shape) != (T, self.N) or buf.dtype != self.dtype or not buf.is_contiguous():
                 raise LgarError("bad output buffer for series %r" % nm)
             res[nm] = buf
-            so.series[j] = buf.data_ptr()
-        w = None
+        stored, block, w = dict(res), None, None
         if basin:
             block = torch.zeros(NACC, T, dtype=torch.float64, device=self.device)
-            so.basin = block.data_ptr()
             for nm in basin:
-                j = ACC_NAMES.index(nm)
-                so.basin_mask |= 1 << j
-                res["basin:" + nm] = block[j]
+                res["basin:" + nm] = block[ACC_NAMES.index(nm)]
                 # a basin sum is taken from the stored series in one deterministic pass after the launch (include/lgar.h:
                 # LgarStepOut.basin); the in-kernel atomics are ~10x as expensive, so a name whose series the caller does
                 # not want still gets a scratch series (kept for the next call of the same shape) unless it would be huge
-                if not so.series[j]:
+                if nm not in stored:
                     if self._basin_scratch[0] != T:  # buffers of one call shape at a time
                         self._basin_scratch = (T, {})
                     scratch = self._basin_scratch[1].get(nm)
                     one = T * self.N * self.totals.element_size()
                     if scratch is None and (len(self._basin_scratch[1]) + 1) * one <= self.basin_scratch_bytes:
-                        scratch = self._basin_scratch[1][nm] = torch.empty(T, self.N, dtype=self.dtype, device=self.device)
+                        scratch = self._basin_scratch[1][nm] = self._new_series(T, self.N, dtype=self.dtype, device=self.device)
                     if scratch is not None:
-                        so.series[j] = scratch.data_ptr()
+                        stored[nm] = scratch
             if weights is not None:
                 w = torch.as_tensor(weights).to(self.device, self.dtype).contiguous()
                 if tuple(w.shape) != (self.N,):
                     raise LgarError("weights must be [N]")
-                so.weights = w.data_ptr()
-        so.counters = self.counters.data_ptr()
         if call_sums:
             res["call_sums"] = torch.zeros(NACC, self.N, dtype=self.dtype, device=self.device)
-            so.call_sums = res["call_sums"].data_ptr()
-        self.dims.n_steps = T
+        so = self._step_out(stored, block, basin, w, res.get("call_sums"))
         fo = _capi.LgarForcing(precip.data_ptr(), pet.data_ptr())
-        with torch.cuda.device(self.device):
-            rc = self.lib.lgar_forward(C.byref(self.dims), C.byref(self._params), C.byref(self._state), C.byref(fo),
-                                       C.byref(so), self.status.data_ptr(), self._dt, self._stream())
-        _capi.check(rc, "lgar_forward")
+        self._call("forward", C.byref(self.dims), C.byref(self._params), C.byref(self._state), C.byref(fo), C.byref(so),
+                   self.status.data_ptr())
         if check:
             self.check_status()
         return res
@@ -238,8 +278,7 @@ class LgarEngine:
 
         precip_row / pet_row: length-N sequences or tensors (cm/h).  Returns (call_sums [NACC, N], runoff [N], percolation [N],
         status [N]) as views of the pinned host buffers, valid until the next call."""
-        if self._state is None:
-            raise LgarError("this engine was created with with_state=False (tangent launches only)")
+        self._need_state()
         st = getattr(self, "_row_stepper", None)
         if st is None:
             N, dev = self.N, self.device
@@ -249,26 +288,24 @@ class LgarEngine:
             st["d_out"] = torch.zeros(NACC + 2, N, dtype=self.dtype, device=dev)  # call_sums rows, then runoff, percolation
             st["h_out"] = torch.zeros(NACC + 2, N, dtype=self.dtype).pin_memory()
             st["h_status"] = torch.zeros(N, dtype=torch.int32).pin_memory()
-            so = _capi.LgarStepOut()
-            so.series[ACC_NAMES.index("runoff")] = st["d_out"][NACC].data_ptr()
-            so.series[ACC_NAMES.index("percolation")] = st["d_out"][NACC + 1].data_ptr()
-            so.call_sums = st["d_out"].data_ptr()
-            so.counters = self.counters.data_ptr()
-            st["so"] = so
-            st["fo"] = _capi.LgarForcing(st["d_in"][0].data_ptr(), st["d_in"][1].data_ptr())
+            so = self._step_out({"runoff": st["d_out"][NACC], "percolation": st["d_out"][NACC + 1]}, call_sums=st["d_out"])
+            fo = _capi.LgarForcing(st["d_in"][0].data_ptr(), st["d_in"][1].data_ptr())
+            st["structs"] = (so, fo)  # (byref keeps no reference of its own)
+            st["args"] = (C.byref(self.dims), C.byref(self._params), C.byref(self._state), C.byref(fo), C.byref(so),
+                          self.status.data_ptr())
         h_in = st["h_in"]
         h_in[0, 0] = torch.as_tensor(precip_row, dtype=self.dtype)
         h_in[1, 0] = torch.as_tensor(pet_row, dtype=self.dtype)
         d = self.dims
         d.n_steps, d.forcing_columns, d.forcing_group = 1, self.N, 1
         with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
             st["d_in"].copy_(h_in, non_blocking=True)
-            rc = self.lib.lgar_forward(C.byref(d), C.byref(self._params), C.byref(self._state), C.byref(st["fo"]),
-                                       C.byref(st["so"]), self.status.data_ptr(), self._dt, self._stream())
-            _capi.check(rc, "lgar_forward")
+            # (the library itself, not _call: entering the device context a second time costs 2 of a call's 115 us)
+            _capi.check(self.lib.lgar_forward(*st["args"], self._dt, C.c_void_p(stream.cuda_stream)), "lgar_forward")
             st["h_out"].copy_(st["d_out"], non_blocking=True)
             st["h_status"].copy_(self.status, non_blocking=True)
-            torch.cuda.current_stream(self.device).synchronize()
+            stream.synchronize()
         return st["h_out"][:NACC], st["h_out"][NACC], st["h_out"][NACC + 1], st["h_status"]
 
     def raise_for_status(self, status_host):
@@ -288,8 +325,8 @@ class LgarEngine:
         grad[c] = sum_t w_runoff[t, c] * d runoff_t[c] + w_perc[t, c] * d percolation_t[c].  status != 0 marks columns whose
         tangent integration faulted (their grad entry is not a gradient): callers must check it (autograd.parameter_vjp does)."""
         prep = lambda t: None if t is None else torch.as_tensor(t).to(self.device, self.dtype).contiguous()
-        precip, pet, w_runoff, w_perc = prep(precip), prep(pet), prep(w_runoff), prep(w_perc)
-        self._set_forcing_layout(precip, pet, forcing_group)
+        precip, pet = self._forcing(precip, pet, forcing_group)
+        w_runoff, w_perc = prep(w_runoff), prep(w_perc)
         share = int(share)
         if share != 0 and (not 2 <= share <= 32 or self.N % share != 0):
             raise LgarError("share must be 0 or 2..32 (with n_columns a multiple of it)")
@@ -312,19 +349,14 @@ class LgarEngine:
         for k, v in dirs.items():
             if v is not None and tuple(v.shape) != (self.L, self.N):
                 raise LgarError("direction[%r] must be [L, N]" % k)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        dstruct = _capi.LgarParams(ptr(dirs["alpha"]), ptr(dirs["n"]), ptr(dirs["ksat"]), None, None, None)
+        dstruct = _capi.LgarParams(_ptr(dirs["alpha"]), _ptr(dirs["n"]), _ptr(dirs["ksat"]), None, None, None)
         grad = torch.zeros(self.N, dtype=self.dtype, device=self.device)
-        ser = torch.empty(T, self.N, dtype=self.dtype, device=self.device) if want_series else None
+        ser = self._new_series(T, self.N, dtype=self.dtype, device=self.device) if want_series else None
         st = torch.zeros(self.N, dtype=torch.int32, device=self.device)
         tickets = torch.zeros(_capi.NTICKETS, dtype=torch.int32, device=self.device)  # persistent-wave work counters
-        self.dims.n_steps = T
         fo = _capi.LgarForcing(precip.data_ptr(), pet.data_ptr())
-        with torch.cuda.device(self.device):
-            rc = self.lib.lgar_forward_tangent(C.byref(self.dims), C.byref(self._params), C.byref(dstruct), C.byref(fo),
-                                               ptr(w_runoff), ptr(w_perc), grad.data_ptr(), ptr(ser), st.data_ptr(),
-                                               self._dt, self._stream(), tickets.data_ptr())
-        _capi.check(rc, "lgar_forward_tangent")
+        self._call("forward_tangent", C.byref(self.dims), C.byref(self._params), C.byref(dstruct), C.byref(fo), _ptr(w_runoff),
+                   _ptr(w_perc), grad.data_ptr(), _ptr(ser), st.data_ptr(), counters=tickets)
         return grad, ser, st
 
     def cooperating_lanes(self):
@@ -340,19 +372,15 @@ class LgarEngine:
 
     def check_status(self):
         """Raise like the reference does (ValueError) if any column hit a physics fault."""
-        if not bool((self.status != 0).any()):
+        st = self.status
+        if not bool((st != 0).any()):
             return
-        bad = int((self.status != 0).sum().item())
-        if bad:
-            bits = int(torch.bitwise_or(self.status, torch.zeros_like(self.status)).max().item())
-            allbits = 0
-            for b in _capi.STATUS_NAMES:
-                if int(((self.status & b) != 0).sum().item()):
-                    allbits |= b
-            names = [v for b, v in _capi.STATUS_NAMES.items() if allbits & b]
-            first = int(torch.nonzero(self.status)[0].item())
-            raise LgarStatusError("%d of %d columns faulted (%s); first column %d, max status %d"
-                                  % (bad, self.N, ", ".join(names), first, bits))
+        bad = torch.nonzero(st)[:, 0]
+        kinds = torch.tensor(list(_capi.STATUS_NAMES), dtype=st.dtype, device=st.device)
+        present = ((st[bad, None] & kinds) != 0).any(0).tolist()  # the fault bits set in any column
+        names = [nm for nm, there in zip(_capi.STATUS_NAMES.values(), present) if there]
+        raise LgarStatusError("%d of %d columns faulted (%s); first column %d, max status %d"
+                              % (bad.numel(), self.N, ", ".join(names), int(bad[0].item()), int(st.max().item())))
 
     # ------------------------------------------------------------------------------------------
     def fronts(self):
@@ -367,8 +395,7 @@ class LgarEngine:
     def _moisture_bins(self, edges, what):
         """Host-side checks of soil_moisture's bins (the library never reads device memory on the host, so the C-ABI takes the
         caller's word for the edges): returns (device fp64 edges or None, number of bins)."""
-        if self._state is None:
-            raise LgarError("this engine was created with with_state=False (tangent launches only)")
+        self._need_state()
         if what not in _capi.MOIST_WHAT:
             raise LgarError("what must be 'theta' or 'storage' (got %r)" % (what,))
         if edges is None:
@@ -386,12 +413,8 @@ class LgarEngine:
         return e.to(self.device).contiguous(), e.numel() - 1
 
     def _moisture_launch(self, e_dev, n_bins, what, out, w, sums):
-        ptr = lambda t: None if t is None else t.data_ptr()
-        with torch.cuda.device(self.device):
-            rc = self.lib.lgar_soil_moisture(C.byref(self.dims), C.byref(self._params), C.byref(self._state), ptr(e_dev),
-                                             n_bins, _capi.MOIST_WHAT[what], out.data_ptr(), ptr(w), ptr(sums), self._dt,
-                                             self._stream())
-        _capi.check(rc, "lgar_soil_moisture")
+        self._call("soil_moisture", C.byref(self.dims), C.byref(self._params), C.byref(self._state), _ptr(e_dev), n_bins,
+                   _capi.MOIST_WHAT[what], out.data_ptr(), _ptr(w), _ptr(sums))
 
     def _moisture_weights(self, weights):
         if weights is None:
@@ -448,11 +471,7 @@ class LgarEngine:
         if every < 1:
             raise LgarError("every must be >= 1")
         e_dev, D = self._moisture_bins(edges, what)
-        precip = torch.as_tensor(precip).to(self.device, self.dtype).contiguous()
-        pet = torch.as_tensor(pet).to(self.device, self.dtype).contiguous()
-        if precip.dim() == 1:
-            precip, pet = precip[None, :], pet[None, :]
-        self._set_forcing_layout(precip, pet, forcing_group)
+        precip, pet = self._forcing(precip, pet, forcing_group)
         T = precip.shape[0]
         series = tuple(series)
         # (zeros: a row no kernel writes -- a column that had faulted before the window -- must read zero in the replay)
@@ -475,13 +494,8 @@ class LgarEngine:
                              weights=weights, forcing_group=forcing_group)
             for nm in basin:
                 rows[nm].append(o["basin:" + nm])
-            stored = _capi.LgarStepOut()
-            for nm in summed:
-                stored.series[ACC_NAMES.index(nm)] = out[nm].data_ptr()
-            with torch.cuda.device(self.device):
-                rc = self.lib.lgar_totals_replay(C.byref(self.dims), C.byref(stored), hi - lo, running.data_ptr(), self._dt,
-                                                 self._stream())
-            _capi.check(rc, "lgar_totals_replay")
+            stored = self._step_out({nm: out[nm] for nm in summed})
+            self._call("totals_replay", C.byref(self.dims), C.byref(stored), hi - lo, running.data_ptr())
             if hi - lo == every:
                 self._moisture_launch(e_dev, D, what, snaps[lo // every], None, None)
         if T:
@@ -525,10 +539,9 @@ def leaf_batch(op, x, y=None, z=0.0, *, alpha, n, ksat, theta_e, theta_r, nint=1
     prep = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float64).to(dev, dtype).contiguous()
     x, y, alpha, n, ksat, theta_e, theta_r = map(prep, (x, y, alpha, n, ksat, theta_e, theta_r))
     out = torch.empty_like(x)
-    ptr = lambda t: None if t is None else t.data_ptr()
     with torch.cuda.device(dev):
-        rc = lib.lgar_leaf_batch(ops[op], x.numel(), ptr(x), ptr(y), float(z), ptr(alpha), ptr(n), ptr(ksat),
-                                 ptr(theta_e), ptr(theta_r), int(nint), float(wilting_point_psi), ptr(out),
+        rc = lib.lgar_leaf_batch(ops[op], x.numel(), _ptr(x), _ptr(y), float(z), _ptr(alpha), _ptr(n), _ptr(ksat),
+                                 _ptr(theta_e), _ptr(theta_r), int(nint), float(wilting_point_psi), _ptr(out),
                                  _capi.F64 if dtype == torch.float64 else _capi.F32,
                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     _capi.check(rc, "lgar_leaf_batch")

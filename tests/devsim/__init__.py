@@ -1,8 +1,10 @@
-"""TEST INFRASTRUCTURE ONLY: ctypes front-end of the device-code simulator (tests/devsim/devsim.cpp).
+"""TEST INFRASTRUCTURE ONLY: the device-code simulator (tests/devsim/devsim.cpp) and the engine that runs on it.
 
 The simulator is lgar_py_amd/csrc's device code (column physics, per-lane kernel bodies, front-capacity chain) compiled
-for the host with -DLGAR_DEVSIM, one lane at a time.  CPU tests use it to run the code the GPU executes against the
-reference's golden vectors.  Never imported by the product package; never timed.
+for the host with -DLGAR_DEVSIM, one lane at a time.  SimEngine is the product's LgarEngine with that library in the HIP
+library's place, so CPU tests run the code the GPU executes against the reference's golden vectors, and the product's own
+host code -- argument checks, struct filling, the model, the autograd tape, the agent (install()) -- without a GPU.
+Never imported by the product package; never timed.
 """
 import ctypes as C
 import hashlib
@@ -11,12 +13,14 @@ import subprocess
 import threading
 
 import numpy as np
+import torch
 
 import _hostbuild
 from _hostbuild import CLANG, CSRC, ROOT  # noqa: F401
 # the one mirror of include/lgar.h (tests/test_capi_host.py checks it against the header)
-from lgar_py_amd._capi import (ACC_NAMES, FMAX, GMAX, NACC, NCOUNTERS, NSCAL, LgarDims, LgarForcing, LgarParams,  # noqa: F401
-                               LgarState, LgarStepOut, make_dims)
+from lgar_py_amd import _capi
+from lgar_py_amd._capi import ACC_NAMES, LgarDims, LgarError, LgarForcing, LgarParams, LgarState, LgarStepOut  # noqa: F401
+from lgar_py_amd.engine import LgarEngine
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _libs = {}
@@ -62,104 +66,44 @@ def prebuild(layers=(2, 3, 4)):
         list(ex.map(lib, layers))
 
 
-class SimEngine:
-    """Host-memory twin of lgar_py_amd.engine.LgarEngine running the simulator (numpy arrays, same layouts)."""
+class SimEngine(LgarEngine):
+    """lgar_py_amd.engine.LgarEngine with the simulator in the library's place: torch CPU tensors, the devsim_* entry points.
+    Everything about the calling surface is the product's own code.  Also takes numpy dtypes and geff_mode=0|1 for
+    geff_precision; forward() does not raise on a faulted column unless asked (check=True): tests read `status`.
+    basin_scratch_bytes defaults to 0: the simulator sums basins in the kernel body, a scratch series would be dead weight."""
 
-    def __init__(self, alpha, n, ksat, theta_e, theta_r, thickness, *, n_columns=None, dt_h=1.0, num_subcycles=1,
-                 initial_psi=2000.0, ponded_depth_max=0.0, wilting_point_psi=15495.0, frozen_factor=1.0, nint=120,
-                 giuh_ordinates=(0.06, 0.51, 0.28, 0.12, 0.03), dtype=np.float64, iter_cap=0, search_mode=1, bottom_mode=0,
-                 use_closed_form_G=False, front_slots=None, geff_mode=0):
-        self.dtype = np.dtype(dtype)
-        self._dt = 1 if self.dtype == np.float64 else 0
+    _new_series = staticmethod(torch.zeros)  # whole buffers are compared bit for bit, rows no kernel writes included
 
-        def prep(x):
-            t = np.asarray(x, dtype=np.float64)
-            if t.ndim == 1:
-                t = np.repeat(t[:, None], n_columns, axis=1)
-            return np.ascontiguousarray(t.astype(self.dtype))
+    def __init__(self, *params, dtype=torch.float64, geff_mode=None, basin_scratch_bytes=0, **kw):
+        if geff_mode is not None:
+            kw["geff_precision"] = "f32" if geff_mode else "native"
+        if not isinstance(dtype, torch.dtype):
+            dtype = {"float64": torch.float64, "float32": torch.float32}.get(np.dtype(dtype).name, dtype)
+        super().__init__(*params, dtype=dtype, basin_scratch_bytes=basin_scratch_bytes, **kw)
 
-        self.alpha, self.n, self.ksat = prep(alpha), prep(n), prep(ksat)
-        self.theta_e, self.theta_r, self.thickness = prep(theta_e), prep(theta_r), prep(thickness)
-        L, N = self.alpha.shape
-        self.L, self.N = L, N
-        self.lib = lib(L)
-        d = self.dims = make_dims(
-            n_columns=N, n_layers=L, dt_h=dt_h, num_subcycles=num_subcycles, initial_psi=initial_psi,
-            ponded_depth_max=ponded_depth_max, wilting_point_psi=wilting_point_psi, frozen_factor=frozen_factor, nint=nint,
-            giuh_ordinates=giuh_ordinates, iter_cap=iter_cap, search_mode=search_mode, bottom_mode=bottom_mode,
-            use_closed_form_G=use_closed_form_G, front_slots=front_slots, geff_mode=geff_mode)
-        F = d.front_slots
-        z = lambda *s, dt=self.dtype: np.zeros(s, dtype=dt)
-        self.depth, self.theta, self.psi, self.k, self.dzdt = z(F, N), z(F, N), z(F, N), z(F, N), z(F, N)
-        self.flags, self.n_fronts = z(F, N, dt=np.uint8), z(N, dt=np.int32)
-        self.scalars, self.totals, self.status = z(NSCAL, N), z(NACC, N), z(N, dt=np.int32)
-        self.counters = z(NCOUNTERS, dt=np.uint64)
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-        self._params = LgarParams(*[ptr(t) for t in (self.alpha, self.n, self.ksat, self.theta_e, self.theta_r, self.thickness)])
-        self._state = LgarState(*[ptr(t) for t in (self.depth, self.theta, self.psi, self.k, self.dzdt, self.flags,
-                                                   self.n_fronts, self.scalars, self.totals)] + [None])
-        self.reset()
+    def forward(self, precip, pet, series=("runoff", "percolation"), out=None, check=False, **kw):
+        return super().forward(precip, pet, series, out, check, **kw)
 
-    def reset(self):
-        rc = self.lib.devsim_state_init(C.byref(self.dims), C.byref(self._params), C.byref(self._state),
-                                        self.status.ctypes.data_as(C.c_void_p), self._dt)
-        assert rc == 0, rc
+    def _open(self, n_layers, device):
+        return lib(n_layers), torch.device("cpu")
 
-    def forward(self, precip, pet, series=("runoff", "percolation"), basin=(), weights=None, call_sums=False, forcing_group=1):
-        precip = np.ascontiguousarray(np.asarray(precip, dtype=np.float64).astype(self.dtype))
-        pet = np.ascontiguousarray(np.asarray(pet, dtype=np.float64).astype(self.dtype))
-        T = precip.shape[0]
-        assert precip.shape == pet.shape and self.N % (precip.shape[1] * forcing_group) == 0
-        self.dims.forcing_columns = precip.shape[1]
-        self.dims.forcing_group = forcing_group
-        res, so = {}, LgarStepOut()
-        for nm in series:
-            buf = np.zeros((T, self.N), dtype=self.dtype)
-            res[nm] = buf
-            so.series[ACC_NAMES.index(nm)] = buf.ctypes.data_as(C.c_void_p)
-        keep = []
-        if basin:
-            block = np.zeros((NACC, T))
-            so.basin = block.ctypes.data_as(C.c_void_p)
-            for nm in basin:
-                so.basin_mask |= 1 << ACC_NAMES.index(nm)
-                res["basin:" + nm] = block[ACC_NAMES.index(nm)]
-            if weights is not None:
-                w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).astype(self.dtype))
-                keep.append(w)
-                so.weights = w.ctypes.data_as(C.c_void_p)
-        so.counters = self.counters.ctypes.data_as(C.c_void_p)
-        if call_sums:
-            res["call_sums"] = np.zeros((NACC, self.N), dtype=self.dtype)
-            so.call_sums = res["call_sums"].ctypes.data_as(C.c_void_p)
-        self.dims.n_steps = T
-        fo = LgarForcing(precip.ctypes.data_as(C.c_void_p), pet.ctypes.data_as(C.c_void_p))
-        rc = self.lib.devsim_forward(C.byref(self.dims), C.byref(self._params), C.byref(self._state), C.byref(fo), C.byref(so),
-                                     self.status.ctypes.data_as(C.c_void_p), self._dt)
-        assert rc == 0, rc
-        return res
+    def _call(self, name, *args, counters=None):
+        fn = getattr(self.lib, "devsim_" + {"forward_tangent": "tangent"}.get(name, name), None)
+        if fn is None:
+            raise LgarError("the device-code simulator has no lgar_%s" % name)
+        _capi.check(fn(*args, self._dt), "devsim: lgar_" + name)
 
-    def tangent(self, direction, precip, pet, w_runoff=None, w_perc=None, want_series=False, forcing_group=1):
-        prep = lambda t: None if t is None else np.ascontiguousarray(np.asarray(t, dtype=np.float64).astype(self.dtype))
-        precip, pet, w_runoff, w_perc = prep(precip), prep(pet), prep(w_runoff), prep(w_perc)
-        T = precip.shape[0]
-        assert self.N % (precip.shape[1] * forcing_group) == 0
-        self.dims.forcing_columns = precip.shape[1]
-        self.dims.forcing_group = forcing_group
-        dirs = {k: prep(direction.get(k)) for k in ("alpha", "n", "ksat")}
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        dstruct = LgarParams(ptr(dirs["alpha"]), ptr(dirs["n"]), ptr(dirs["ksat"]), None, None, None)
-        grad = np.zeros(self.N, dtype=self.dtype)
-        ser = np.zeros((T, self.N), dtype=self.dtype) if want_series else None
-        st = np.zeros(self.N, dtype=np.int32)
-        self.dims.n_steps = T
-        fo = LgarForcing(ptr(precip), ptr(pet))
-        rc = self.lib.devsim_tangent(C.byref(self.dims), C.byref(self._params), C.byref(dstruct), C.byref(fo), ptr(w_runoff),
-                                     ptr(w_perc), ptr(grad), ptr(ser), ptr(st), self._dt)
-        assert rc == 0, rc
-        return grad, ser, st
+    def step_rows_host(self, precip_row, pet_row):
+        a = lambda t: torch.as_tensor(t, dtype=torch.float64).reshape(1, -1)
+        res = self.forward(a(precip_row), a(pet_row), series=("runoff", "percolation"), call_sums=True)
+        return res["call_sums"], res["runoff"][0], res["percolation"][0], self.status.clone()
 
-    def fronts(self):
-        fl = self.flags
-        return dict(depth=self.depth, theta=self.theta, psi=self.psi, k=self.k, dzdt=self.dzdt,
-                    layer=(fl & 0x7F).astype("int8"), to_bottom=(fl >> 7).astype("int8"), n_fronts=self.n_fronts)
+    def cooperating_lanes(self):
+        raise LgarError("the device-code simulator has no lgar_cooperating_lanes")
+
+
+def install():
+    """Put the simulator behind the model and the autograd tape (in THIS process)."""
+    import lgar_py_amd.autograd as A
+    import lgar_py_amd.model as M
+    M.LgarEngine = A.LgarEngine = SimEngine

@@ -15,17 +15,12 @@ def variant_lib(n_layers, flags):
 class VariantEngine(devsim.SimEngine):
     """devsim.SimEngine running a variant library (forward path only)."""
 
-    def __init__(self, flags, alpha, *args, **kw):
+    def __init__(self, flags, *params, **kw):
         self._variant_flags = tuple(flags)
-        self._variant = None
-        super().__init__(alpha, *args, **kw)
+        super().__init__(*params, **kw)
 
-    # SimEngine.__init__ stores the plain library in self.lib and calls reset(): the variant takes its place from then on
-    def reset(self):
-        if self._variant is None:
-            self._variant = variant_lib(self.L, self._variant_flags)
-        self.lib = self._variant
-        super().reset()
+    def _open(self, n_layers, device):
+        return variant_lib(n_layers, self._variant_flags), super()._open(n_layers, device)[1]
 
 
 def prebuild(n_layers, flag_sets):

@@ -1,7 +1,7 @@
 """CPU, world_size 2 (gloo): shared-parameter training with the basin's columns sharded over the ranks
 (lgar_py_amd.agent.DifferentiableLGAR under a process group; reference loop: agents/DifferentiableLGAR.py:94-172, SURVEY.md
 section 8e: "training with shared parameters adds an all-reduce of L x 3 gradient scalars").  The compute engine is injected:
-the device code compiled for the host (tests/devsim behind tests/_sim_lgar_engine.SimLgarEngine) stands in for the HIP engine,
+the device code compiled for the host (devsim.SimEngine, put in place by tests/_sim_lgar_engine.install()) stands in for the HIP engine,
 so model, autograd tape, tangent launches and the agent's two exchanges all run here; on GPUs the same code runs with backend
 "nccl" (= RCCL; tests/test_gpu_distributed.py)."""
 import os

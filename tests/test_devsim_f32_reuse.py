@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+from _golden import engine_keywords
 from conftest import GOLDEN
 
 SWITCHES = ["-DLGAR_NO_DZDT_MEMO", "-DLGAR_NO_F32_RARE_GEFF", "-DLGAR_NO_GEFF_ENDS"]
@@ -34,10 +35,7 @@ def _run(name, flags, search_mode):
     T = g["forcing"].shape[0] if crash < 0 else crash + 1
     f = g["forcing"][:T]
     eng = variants.VariantEngine(flags, g["alpha"], g["n"], g["ksat"], g["theta_e"], g["theta_r"], g["thickness"], n_columns=1,
-                                 dt_h=float(g["dt_h"]), num_subcycles=int(g["num_subcycles"]), ponded_depth_max=float(g["pdm"]),
-                                 initial_psi=float(g["initial_psi"]), wilting_point_psi=float(g["wilting_point_psi"]),
-                                 frozen_factor=float(g["frozen_factor"]), nint=int(g["nint"]),
-                                 giuh_ordinates=tuple(g["giuh_ordinates"]), dtype=np.float32, search_mode=search_mode)
+                                 dtype=np.float32, search_mode=search_mode, **engine_keywords(g))
     out = eng.forward(f[:, 0:1], f[:, 1:2], series=devsim.ACC_NAMES, call_sums=True)
     res = {"series:" + nm: _bits(out[nm]) for nm in devsim.ACC_NAMES}
     res["call_sums"] = _bits(out["call_sums"])

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+from _golden import engine_keywords
 from conftest import check_fault_kind, GOLDEN, golden_names
 
 
@@ -14,14 +15,19 @@ def _rel(a, b, floor=1e-6):
     return np.abs(a - b) / np.maximum(np.abs(b), floor)
 
 
+def _np(x):
+    """An engine's tensors (one, or the dict / tuple forward() / tangent() return) as numpy arrays for the comparisons."""
+    if isinstance(x, dict):
+        return {k: _np(v) for k, v in x.items()}
+    if isinstance(x, tuple):
+        return tuple(_np(v) for v in x)
+    return x if x is None else x.numpy()
+
+
 def _engine(g, ncol, dtype=np.float64, **kw):
     import devsim
     return devsim.SimEngine(g["alpha"], g["n"], g["ksat"], g["theta_e"], g["theta_r"], g["thickness"], n_columns=ncol,
-                            dt_h=float(g["dt_h"]), num_subcycles=int(g["num_subcycles"]), ponded_depth_max=float(g["pdm"]),
-                            initial_psi=float(g["initial_psi"]), wilting_point_psi=float(g["wilting_point_psi"]),
-                            frozen_factor=float(g["frozen_factor"]), nint=int(g["nint"]),
-                            giuh_ordinates=tuple(g["giuh_ordinates"]), dtype=dtype,
-                            use_closed_form_G=bool(g["closed_form"]) if "closed_form" in g.files else False, **kw)
+                            dtype=dtype, **engine_keywords(g), **kw)
 
 
 TRAJ = [n for n in golden_names() if not n.startswith("grad_")]
@@ -37,7 +43,7 @@ def test_device_code_fp64_trajectory_vs_reference_golden(name, mode):
     eng = _engine(g, 2, search_mode=mode)
     assert abs(float(eng.scalars[2, 0]) - float(g["init_volume"])) <= 1e-9
     f = g["forcing"][:T]
-    out = eng.forward(np.repeat(f[:, 0:1], 2, 1), np.repeat(f[:, 1:2], 2, 1), series=devsim.ACC_NAMES, call_sums=True)
+    out = _np(eng.forward(np.repeat(f[:, 0:1], 2, 1), np.repeat(f[:, 1:2], 2, 1), series=devsim.ACC_NAMES, call_sums=True))
     for j, nm in enumerate(devsim.ACC_NAMES):
         assert _rel(out[nm][:, 0], g["acc"][:T, j]).max() <= 1e-6, nm
         assert (out[nm][:, 0] == out[nm][:, 1]).all()
@@ -59,7 +65,7 @@ def test_device_code_fp64_trajectory_vs_reference_golden(name, mode):
         f1 = g["forcing"][T:T + 1]
         eng.forward(np.repeat(f1[:, 0:1], 2, 1), np.repeat(f1[:, 1:2], 2, 1), series=())
         assert (eng.status != 0).all()
-        check_fault_kind(g, eng.status)
+        check_fault_kind(g, _np(eng.status))
 
 
 # (search_mode, geff_mode): fast through the capacity chain, literal, mixed precision; bars on depth / theta relative to the
@@ -86,16 +92,17 @@ def test_device_code_front_table_at_every_step_vs_reference_golden(name, mode):
     f = g["forcing"]
     frec = g["fronts"].shape[1]
     above = 0
+    flags, depth, theta = _np(eng.flags), _np(eng.depth), _np(eng.theta)  # (views of the engine's state)
     for t in range(T):
         eng.forward(f[t:t + 1, 0:1], f[t:t + 1, 1:2], series=())
         nf = int(g["nfronts"][t])
         assert int(eng.n_fronts[0]) == nf, (t, int(eng.n_fronts[0]), nf)
         q = min(nf, frec)
-        fl = eng.flags[:q, 0]
+        fl = flags[:q, 0]
         assert ((fl & 0x7F) == g["front_layer"][t, :q]).all(), t
         assert ((fl >> 7) == g["front_bottom"][t, :q]).all(), t
-        dz = _rel(eng.depth[:q, 0], g["fronts"][t, :q, 0]).max()
-        dth = _rel(eng.theta[:q, 0], g["fronts"][t, :q, 1]).max()
+        dz = _rel(depth[:q, 0], g["fronts"][t, :q, 0]).max()
+        dth = _rel(theta[:q, 0], g["fronts"][t, :q, 1]).max()
         above += int(max(dz, dth) > usual)
         assert dz <= bar and dth <= bar, (t, dz, dth)
     assert above <= max(1, T // 50), (above, T)
@@ -112,7 +119,7 @@ def test_device_code_literal_mode_vs_reference_golden(name):
     T = crash if crash >= 0 else g["forcing"].shape[0]
     eng = _engine(g, 1, search_mode=0)
     f = g["forcing"][:T]
-    out = eng.forward(f[:, 0:1], f[:, 1:2], series=devsim.ACC_NAMES)
+    out = _np(eng.forward(f[:, 0:1], f[:, 1:2], series=devsim.ACC_NAMES))
     for j, nm in enumerate(devsim.ACC_NAMES):
         assert _rel(out[nm][:, 0], g["acc"][:T, j]).max() <= 1e-7, nm  # observed <= 2e-9
     assert int(eng.n_fronts[0]) == int(g["nfronts"][T - 1]) and int(eng.status[0]) == 0
@@ -146,7 +153,7 @@ def test_device_code_mixed_precision_geff_vs_reference_golden(name):
     T = crash if crash >= 0 else g["forcing"].shape[0]
     eng = _engine(g, 2, search_mode=2, geff_mode=1)
     f = g["forcing"][:T]
-    out = eng.forward(np.repeat(f[:, 0:1], 2, 1), np.repeat(f[:, 1:2], 2, 1), series=devsim.ACC_NAMES)
+    out = _np(eng.forward(np.repeat(f[:, 0:1], 2, 1), np.repeat(f[:, 1:2], 2, 1), series=devsim.ACC_NAMES))
     acc = np.stack([out[nm][:, 0] for nm in devsim.ACC_NAMES], 1)
     mixed_mode_check(acc, g["acc"][:T], T)
     assert all((out[nm][:, 0] == out[nm][:, 1]).all() for nm in devsim.ACC_NAMES)
@@ -162,7 +169,7 @@ def test_device_code_mixed_precision_geff_vs_reference_golden(name):
         f1 = g["forcing"][T:T + 1]
         eng.forward(np.repeat(f1[:, 0:1], 2, 1), np.repeat(f1[:, 1:2], 2, 1), series=())
         assert (eng.status != 0).all()
-        check_fault_kind(g, eng.status)
+        check_fault_kind(g, _np(eng.status))
 
 
 def test_mixed_precision_geff_leaf_accuracy():
@@ -210,12 +217,12 @@ def test_mixed_precision_flags_the_columns_the_oracle_flags():
                                     pdm=0.0, dt_h=300.0 / 3600.0)
     eng = devsim.SimEngine(P["alpha"], P["n"], P["ksat"], P["theta_e"], P["theta_r"], P["thickness"], dt_h=300.0 / 3600.0,
                            ponded_depth_max=0.0, search_mode=1, geff_mode=1)
-    out = eng.forward(pr, pe, series=("runoff",))
-    assert ((st != 0) == (eng.status != 0)).all()
+    out = _np(eng.forward(pr, pe, series=("runoff",)))
+    assert ((st != 0) == (_np(eng.status) != 0)).all()
     ok = st == 0
     assert np.abs(out["runoff"][:, ok] - ro[:, ok]).max() <= MIXED_FLUX * max(1.0, np.abs(ro).max())
     scale = np.maximum(np.maximum(np.abs(acc[:8]), acc[0:1]), 1e-2)  # a column's totals against its water input
-    assert (np.abs(eng.totals[:8] - acc[:8]) / scale)[:, ok].max() <= MIXED_TOTAL
+    assert (np.abs(_np(eng.totals)[:8] - acc[:8]) / scale)[:, ok].max() <= MIXED_TOTAL
 
 
 def test_capacity_chain_hands_columns_over_and_resumes():
@@ -228,10 +235,10 @@ def test_capacity_chain_hands_columns_over_and_resumes():
     pr = g["forcing"][:T, 0:1] * scale[None, :]
     pe = np.zeros_like(pr)
     a = _engine(g, N, search_mode=1)
-    ref = a.forward(pr, pe, series=devsim.ACC_NAMES, basin=("runoff", "infiltration"), call_sums=True)
+    ref = _np(a.forward(pr, pe, series=devsim.ACC_NAMES, basin=("runoff", "infiltration"), call_sums=True))
     assert a.n_fronts.max() > 16 and a.n_fronts.min() == 3 and (a.status == 0).all()
     b = _engine(g, N, search_mode=2)
-    got = b.forward(pr, pe, series=devsim.ACC_NAMES, basin=("runoff", "infiltration"), call_sums=True)
+    got = _np(b.forward(pr, pe, series=devsim.ACC_NAMES, basin=("runoff", "infiltration"), call_sums=True))
     for nm in ref:
         if nm.startswith("basin") or nm == "call_sums":  # sums are split at the hand-over points: last-bit differences
             assert np.allclose(got[nm], ref[nm], rtol=1e-13, atol=1e-15), nm
@@ -239,17 +246,17 @@ def test_capacity_chain_hands_columns_over_and_resumes():
             assert np.array_equal(got[nm], ref[nm]), nm
     for x, y in ((a.depth, b.depth), (a.theta, b.theta), (a.psi, b.psi), (a.dzdt, b.dzdt), (a.flags, b.flags),
                  (a.n_fronts, b.n_fronts), (a.scalars, b.scalars), (a.status, b.status)):
-        assert np.array_equal(x, y)
-    assert np.allclose(a.totals, b.totals, rtol=1e-14, atol=0)
+        assert np.array_equal(_np(x), _np(y))
+    assert np.allclose(_np(a.totals), _np(b.totals), rtol=1e-14, atol=0)
     c = _engine(g, N, search_mode=2)  # ragged chunks: hand-overs happen in different calls
     parts = []
     for lo, hi in ((0, 7), (7, 30), (30, 31), (31, 70), (70, 84)):
-        parts.append(c.forward(pr[lo:hi], pe[lo:hi], series=("runoff", "ending_volume"), call_sums=True))
+        parts.append(_np(c.forward(pr[lo:hi], pe[lo:hi], series=("runoff", "ending_volume"), call_sums=True)))
         assert (c.status == 0).all()  # LGAR_ST_RESUME never survives a call
     assert np.array_equal(np.concatenate([p["runoff"] for p in parts]), ref["runoff"])
     assert np.array_equal(np.concatenate([p["ending_volume"] for p in parts]), ref["ending_volume"])
     assert np.allclose(sum(p["call_sums"][:8] for p in parts), ref["call_sums"][:8], rtol=1e-13, atol=1e-15)
-    assert np.array_equal(c.n_fronts, a.n_fronts) and np.array_equal(c.depth, a.depth)
+    assert np.array_equal(_np(c.n_fronts), _np(a.n_fronts)) and np.array_equal(_np(c.depth), _np(a.depth))
 
 
 def test_front_overflow_is_flagged_at_the_reference_state_limit():
@@ -281,7 +288,7 @@ def test_device_code_fp32_close_to_reference():
         eng.forward(f[:, 0:1], f[:, 1:2], series=())
         assert int(eng.status[0]) == 0
         ref = g["acc"][:, :8].sum(0)
-        got = eng.totals[:8, 0].astype(np.float64)
+        got = _np(eng.totals)[:8, 0].astype(np.float64)
         scale = max(ref[0], 1.0)  # precipitation scale
         assert np.abs(got - ref).max() <= 5e-3 * scale, (name, got, ref)
         assert abs(float(eng.totals[9, 0]) - g["acc"][-1, 9]) <= 5e-3 * g["acc"][-1, 9]
@@ -301,7 +308,7 @@ def test_device_tangent_matches_reference_autograd(name, mode):
     T = f.shape[0]
     L = len(g["alpha"])
     eng = _engine(g, 1, search_mode=mode)
-    out = eng.forward(f[:, 0:1], f[:, 1:2], series=("runoff",))
+    out = _np(eng.forward(f[:, 0:1], f[:, 1:2], series=("runoff",)))
     r = out["runoff"][:, 0]
     loss = float(np.mean(r * r))
     assert abs(loss - float(g["loss"])) <= 1e-9 * float(g["loss"])
@@ -314,7 +321,7 @@ def test_device_tangent_matches_reference_autograd(name, mode):
         for l in range(L):
             d = np.zeros((L, 1))
             d[l] = 1.0
-            gr, _, st = eng.tangent({kind: d}, f[:, 0:1], f[:, 1:2], w_runoff=w)
+            gr, _, st = _np(eng.tangent({kind: d}, f[:, 0:1], f[:, 1:2], w_runoff=w))
             assert int(st[0]) == 0
             got[l] = gr[0]
         assert np.abs(got - ref).max() <= 1e-6 * np.abs(ref).max(), (kind, got, ref)
@@ -332,12 +339,12 @@ def test_tangent_capacity_chain_and_status():
     w = np.ones((T, N))
     d = np.zeros((3, N))
     d[0] = 1.0
-    g1, _, s1 = _engine(g, N, search_mode=1).tangent({"ksat": d}, pr, pe, w_runoff=w)
-    g2, _, s2 = _engine(g, N, search_mode=2).tangent({"ksat": d}, pr, pe, w_runoff=w)
+    g1, _, s1 = _np(_engine(g, N, search_mode=1).tangent({"ksat": d}, pr, pe, w_runoff=w))
+    g2, _, s2 = _np(_engine(g, N, search_mode=2).tangent({"ksat": d}, pr, pe, w_runoff=w))
     assert (s1 == 0).all() and (s2 == 0).all()
     assert np.array_equal(g1, g2) and g1[0] != 0.0 and g1[1] == 0.0
     long = np.concatenate([np.load(os.path.join(GOLDEN, "manyfronts_pulse_84.npz"))["forcing"][:, 0], np.tile([0.02, 0.0], 30)])[:, None]
-    gl, _, sl = _engine(g, 1, search_mode=2).tangent({"ksat": d[:, :1]}, long, np.zeros_like(long), w_runoff=np.ones_like(long))
+    gl, _, sl = _np(_engine(g, 1, search_mode=2).tangent({"ksat": d[:, :1]}, long, np.zeros_like(long), w_runoff=np.ones_like(long)))
     assert int(sl[0]) & 8
 
 
@@ -360,11 +367,11 @@ def test_columns_outside_the_reference_domain_are_flagged_like_the_oracle():
     for mode in (0, 1, 2):
         eng = devsim.SimEngine(P["alpha"], P["n"], P["ksat"], P["theta_e"], P["theta_r"], P["thickness"], dt_h=300.0 / 3600.0,
                                ponded_depth_max=0.0, search_mode=mode)
-        out = eng.forward(pr, pe, series=("runoff",))
-        assert ((st != 0) == (eng.status != 0)).all(), mode
+        out = _np(eng.forward(pr, pe, series=("runoff",)))
+        assert ((st != 0) == (_np(eng.status) != 0)).all(), mode
         ok = st == 0
         assert np.abs(out["runoff"][:, ok] - ro[:, ok]).max() <= 1e-6 * max(1.0, np.abs(ro).max()), mode
-        assert _rel(eng.totals[:8][:, ok], acc[:8][:, ok], 1e-3).max() <= 1e-6, mode
+        assert _rel(_np(eng.totals)[:8][:, ok], acc[:8][:, ok], 1e-3).max() <= 1e-6, mode
 
 
 def test_forcing_broadcast_equals_replicated_forcing():
@@ -376,34 +383,34 @@ def test_forcing_broadcast_equals_replicated_forcing():
     f = g["forcing"][:200]
     N = 6
     a = _engine(g, N)
-    full = a.forward(np.repeat(f[:, 0:1], N, 1), np.repeat(f[:, 1:2], N, 1), series=("runoff", "AET"))
+    full = _np(a.forward(np.repeat(f[:, 0:1], N, 1), np.repeat(f[:, 1:2], N, 1), series=("runoff", "AET")))
     b = _engine(g, N)
-    one = b.forward(f[:, 0:1], f[:, 1:2], series=("runoff", "AET"))
+    one = _np(b.forward(f[:, 0:1], f[:, 1:2], series=("runoff", "AET")))
     for nm in full:
         assert np.array_equal(full[nm], one[nm])
-    assert np.array_equal(a.theta, b.theta) and np.array_equal(a.totals, b.totals)
+    assert np.array_equal(_np(a.theta), _np(b.theta)) and np.array_equal(_np(a.totals), _np(b.totals))
     sc = np.array([1.0, 0.5, 0.8])
     pr3, pe3 = f[:, 0:1] * sc[None, :], f[:, 1:2] * np.ones((1, 3))
     c = _engine(g, N)
-    half = c.forward(pr3, pe3, series=("runoff",))  # columns 0..2 and 3..5 see forcing columns 0..2
+    half = _np(c.forward(pr3, pe3, series=("runoff",)))  # columns 0..2 and 3..5 see forcing columns 0..2
     d = _engine(g, N)
-    rep = d.forward(np.tile(pr3, (1, 2)), np.tile(pe3, (1, 2)), series=("runoff",))
+    rep = _np(d.forward(np.tile(pr3, (1, 2)), np.tile(pe3, (1, 2)), series=("runoff",)))
     assert np.array_equal(half["runoff"], rep["runoff"])
     w = np.linspace(0.5, 1.5, 200)[:, None] * np.ones((1, 3))
     dirs = np.zeros((3, N))
     dirs[0, :3] = 1.0   # first direction: layer-0 Ksat on columns 0..2
     dirs[1, 3:] = 1.0   # second direction: layer-1 Ksat on columns 3..5 (same soils, same forcing)
-    g1, _, s1 = c.tangent({"ksat": dirs}, pr3, pe3, w_runoff=w)
-    g2, _, s2 = d.tangent({"ksat": dirs}, np.tile(pr3, (1, 2)), np.tile(pe3, (1, 2)), w_runoff=np.tile(w, (1, 2)))
+    g1, _, s1 = _np(c.tangent({"ksat": dirs}, pr3, pe3, w_runoff=w))
+    g2, _, s2 = _np(d.tangent({"ksat": dirs}, np.tile(pr3, (1, 2)), np.tile(pe3, (1, 2)), w_runoff=np.tile(w, (1, 2))))
     assert np.array_equal(g1, g2) and (s1 == 0).all() and np.abs(g1).max() > 0
     # forcing_group: G consecutive columns share a forcing column (the differentiable path's interleaved directions)
     e = _engine(g, N)
-    grp = e.forward(pr3, pe3, series=("runoff",), forcing_group=2)  # columns (0,1), (2,3), (4,5) see forcing columns 0, 1, 2
+    grp = _np(e.forward(pr3, pe3, series=("runoff",), forcing_group=2))  # columns (0,1), (2,3), (4,5) see forcing columns 0, 1, 2
     assert np.array_equal(grp["runoff"], rep["runoff"][:, [0, 3, 1, 4, 2, 5]])
     dirs2 = np.zeros((3, N))
     dirs2[0, 0::2] = 1.0
     dirs2[1, 1::2] = 1.0
-    g3, _, s3 = e.tangent({"ksat": dirs2}, pr3, pe3, w_runoff=w, forcing_group=2)
+    g3, _, s3 = _np(e.tangent({"ksat": dirs2}, pr3, pe3, w_runoff=w, forcing_group=2))
     assert np.array_equal(g3, g2[[0, 3, 1, 4, 2, 5]]) and (s3 == 0).all()
 
 
@@ -437,21 +444,21 @@ def test_giuh_queue_in_place_survives_cut_launches_and_matches_the_reference_que
     cuts = (7, 31, 32, T)
     for geff_mode, bar in ((1, MIXED_FLUX), (0, 1e-9)):
         one = _engine(g, 2, search_mode=2, geff_mode=geff_mode)
-        whole = one.forward(pr, pe, series=devsim.ACC_NAMES)
+        whole = _np(one.forward(pr, pe, series=devsim.ACC_NAMES))
         cut = _engine(g, 2, search_mode=2, geff_mode=geff_mode)
         parts, t0 = [], 0
         scale = max(float(np.abs(g["giuh_queue"]).max()), 1e-6)
         for t1 in cuts:
             if t1 <= t0:
                 continue
-            parts.append(cut.forward(pr[t0:t1], pe[t0:t1], series=devsim.ACC_NAMES))
-            q = cut.scalars[3:3 + ng, 0]
+            parts.append(_np(cut.forward(pr[t0:t1], pe[t0:t1], series=devsim.ACC_NAMES)))
+            q = _np(cut.scalars)[3:3 + ng, 0]
             assert np.abs(q - g["giuh_queue"][t1 - 1]).max() <= bar * scale, (geff_mode, t1)
             assert (cut.scalars[3 + ng:, 0] == 0).all()
             t0 = t1
         for nm in devsim.ACC_NAMES:
             assert np.array_equal(np.concatenate([p[nm] for p in parts], 0), whole[nm]), (geff_mode, nm)
-        assert np.array_equal(cut.scalars, one.scalars) and np.array_equal(cut.status, one.status)
+        assert np.array_equal(_np(cut.scalars), _np(one.scalars)) and np.array_equal(_np(cut.status), _np(one.status))
         a, b = cut.fronts(), one.fronts()
         assert all(np.array_equal(a[k], b[k]) for k in a)
         assert (whole["giuh_runoff"][:, 0] > 0).sum() > 3  # the fixture routes runoff

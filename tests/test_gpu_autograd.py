@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+from _golden import engine_keywords
 from conftest import GOLDEN
 from test_host_io import write_forcing, write_soil_dat
 
@@ -20,10 +21,7 @@ def _setup(g, N, dtype=torch.float64, **kw):
     pe = f[:, 1:2].expand(T, N).contiguous()
     P = {k: torch.tensor(np.repeat(g[k][:, None], N, 1), device="cuda", dtype=dtype) for k in
          ("alpha", "n", "ksat", "theta_e", "theta_r", "thickness")}
-    ekw = dict(dt_h=float(g["dt_h"]), num_subcycles=int(g["num_subcycles"]), ponded_depth_max=float(g["pdm"]), dtype=dtype,
-               initial_psi=float(g["initial_psi"]), wilting_point_psi=float(g["wilting_point_psi"]),
-               frozen_factor=float(g["frozen_factor"]), nint=int(g["nint"]), giuh_ordinates=tuple(g["giuh_ordinates"]),
-               use_closed_form_G=bool(g["closed_form"]) if "closed_form" in g.files else False)
+    ekw = dict(engine_keywords(g), dtype=dtype)
     ekw.update(kw)
     return P, pr, pe, ekw
 

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+from _golden import engine_keywords
 from conftest import GOLDEN
 
 import moisture_host as MH
@@ -18,12 +19,6 @@ torch = pytest.importorskip("torch")
 
 NCOL = 67  # one full wave + a ragged tail
 COLUMN_SEED = 8  # (the oracle keeps 65 and 67 of the 67 columns of the two fixtures valid: test_the_chosen_columns_...)
-
-
-def _golden_kw(g):
-    return dict(dt_h=float(g["dt_h"]), num_subcycles=int(g["num_subcycles"]), ponded_depth_max=float(g["pdm"]),
-                initial_psi=float(g["initial_psi"]), wilting_point_psi=float(g["wilting_point_psi"]),
-                frozen_factor=float(g["frozen_factor"]), nint=int(g["nint"]), giuh_ordinates=tuple(g["giuh_ordinates"]))
 
 
 def perturbed_job(name, N=NCOL, seed=COLUMN_SEED):
@@ -45,14 +40,14 @@ def perturbed_job(name, N=NCOL, seed=COLUMN_SEED):
 def _engine(g, P, dtype, **kw):
     import lgar_py_amd as lg
     return lg.LgarEngine(P["alpha"], P["n"], P["ksat"], P["theta_e"], P["theta_r"], P["thickness"], dtype=dtype,
-                         **dict(_golden_kw(g), **kw))
+                         **dict(engine_keywords(g), **kw))
 
 
 def _replicated(name, ncol, dtype, **kw):
     import lgar_py_amd as lg
     g = np.load(os.path.join(GOLDEN, name + ".npz"))
     eng = lg.LgarEngine(g["alpha"], g["n"], g["ksat"], g["theta_e"], g["theta_r"], g["thickness"], n_columns=ncol, dtype=dtype,
-                        **dict(_golden_kw(g), **kw))
+                        **dict(engine_keywords(g), **kw))
     f = torch.tensor(g["forcing"])
     return g, eng, f[:, 0:1].expand(-1, ncol).contiguous(), f[:, 1:2].expand(-1, ncol).contiguous()
 

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+from _golden import engine_keywords
 from conftest import check_fault_kind, GOLDEN, golden_names
 
 pytestmark = pytest.mark.gpu
@@ -23,11 +24,7 @@ def _rel(a, b, floor=1e-6):
 def _engine(g, ncol, dtype, **kw):
     import lgar_py_amd as lg
     return lg.LgarEngine(g["alpha"], g["n"], g["ksat"], g["theta_e"], g["theta_r"], g["thickness"], n_columns=ncol,
-                         dt_h=float(g["dt_h"]), num_subcycles=int(g["num_subcycles"]),
-                         ponded_depth_max=float(g["pdm"]), initial_psi=float(g["initial_psi"]),
-                         wilting_point_psi=float(g["wilting_point_psi"]), frozen_factor=float(g["frozen_factor"]),
-                         nint=int(g["nint"]), giuh_ordinates=tuple(g["giuh_ordinates"]), dtype=dtype,
-                         use_closed_form_G=bool(g["closed_form"]) if "closed_form" in g.files else False, **kw)
+                         dtype=dtype, **engine_keywords(g), **kw)
 
 
 def _forcing(g, ncol, sl=slice(None)):
