@@ -20,7 +20,7 @@ def main():
     from lgar_py_amd import config
     from lgar_py_amd import workloads as W
     from lgar_py_amd.agent import DifferentiableLGAR
-    from test_host_io import write_forcing, write_soil_dat
+    from _model_files import write_forcing, write_soil_dat
     f = W.synth1_forcing()
     d = os.path.join(tmp, "w%d_r%d" % (world, rank))
     os.makedirs(d, exist_ok=True)

@@ -53,6 +53,26 @@ def profile_ref(depth, theta, layer, n_fronts, thickness, edges=None, what="thet
         return np.where(w > 0, S / w, np.nan)
 
 
+def tables(name, dtype=np.float64):
+    """The reference's front table at every recorded step before its crash, one step per column: arrays laid out like
+    LgarEngine.fronts() plus thickness [L, T], the total thickness Z and the recorded ending_volume [T]."""
+    g = np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))
+    crash = int(g["crash_step"])
+    T = crash if crash >= 0 else g["forcing"].shape[0]
+    lay = g["front_layer"][:T].T
+    t = dict(depth=np.ascontiguousarray(g["fronts"][:T, :, 0].T.astype(dtype)),
+             theta=np.ascontiguousarray(g["fronts"][:T, :, 1].T.astype(dtype)),
+             layer=lay, flags=np.where(lay >= 0, lay, 0).astype(np.uint8), n_fronts=g["nfronts"][:T].astype(np.int32),
+             thickness=np.repeat(g["thickness"].astype(dtype)[:, None], T, axis=1))
+    F = min(t["depth"].shape[0], 32)  # (manyfronts_pulse_84 records 40 slots, 31 in use)
+    assert int(t["n_fronts"].max()) <= F
+    for k in ("depth", "theta", "layer", "flags"):
+        t[k] = np.ascontiguousarray(t[k][:F])
+    t["Z"] = float(np.cumsum(g["thickness"].astype(np.float64))[-1])
+    t["volume"] = g["acc"][:T, 9]
+    return t
+
+
 def same_bits(a, b):
     """Bit-for-bit equality of two float arrays (NaNs must sit in the same places)."""
     a, b = np.asarray(a), np.asarray(b)

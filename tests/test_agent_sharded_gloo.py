@@ -25,7 +25,7 @@ def _agent(tmp, world_rank=None):
     from lgar_py_amd import config
     from lgar_py_amd import workloads as W
     from lgar_py_amd.agent import DifferentiableLGAR
-    from test_host_io import write_forcing, write_soil_dat
+    from _model_files import write_forcing, write_soil_dat
     f = W.synth1_forcing()[:96]
     tag = "single" if world_rank is None else "r%d" % world_rank
     os.makedirs(os.path.join(tmp, tag), exist_ok=True)

@@ -6,9 +6,10 @@ import os
 import numpy as np
 import pytest
 
-from _golden import engine_keywords
+import _golden as G
+from _golden import GRADS, engine_keywords
+from _model_files import write_forcing, write_soil_dat
 from conftest import GOLDEN
-from test_host_io import write_forcing, write_soil_dat
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -24,11 +25,6 @@ def _setup(g, N, dtype=torch.float64, **kw):
     ekw = dict(engine_keywords(g), dtype=dtype)
     ekw.update(kw)
     return P, pr, pe, ekw
-
-
-from conftest import golden_names
-
-GRADS = [n for n in golden_names() if n.startswith("grad_")]
 
 
 @pytest.mark.parametrize("name", GRADS)
@@ -52,19 +48,13 @@ def test_gradients_match_reference_autograd(name, mode, shared, monkeypatch):
     assert runoff.requires_grad
     assert runoff.grad_fn is not None
     loss = torch.mean(runoff[:, 0] ** 2)
-    assert abs(float(loss) - float(g["loss"])) <= 1e-9 * float(g["loss"])
     # torch.autograd.grad works like for the reference's graph (models/dpLGAR.py:299), and so does backward()
-    ga, gn, gk = torch.autograd.grad(loss, [P["alpha"], P["n"], P["ksat"]], retain_graph=True)
+    direct = dict(zip(("alpha", "n", "ksat"), torch.autograd.grad(loss, [P["alpha"], P["n"], P["ksat"]], retain_graph=True)))
     loss.backward()
-    for k, ref, direct in (("alpha", g["d_alpha"], ga), ("n", g["d_n"], gn), ("ksat", g["d_ksat"], gk)):
-        got = P[k].grad[:, 0].cpu().numpy()
-        ref = np.nan_to_num(ref, nan=0.0)  # None in the reference = no dependence
-        if k == "ksat":  # the reference's Parameter is Ksat x frozen_factor (models/dpLGAR.py:57), the engine's input is Ksat
-            ref = ref * float(g["frozen_factor"])
-        scale = np.abs(ref).max()
-        assert np.abs(got - ref).max() <= 1e-6 * scale, (k, got, ref)
+    G.check_gradients(g, float(loss), {k: P[k].grad[:, 0].cpu().numpy() for k in direct})
+    for k in direct:
         assert np.abs(P[k].grad[:, 1:].cpu().numpy()).max() == 0.0  # other columns do not enter the loss
-        assert torch.equal(direct, P[k].grad)
+        assert torch.equal(direct[k], P[k].grad)
 
 
 def test_tangent_matches_finite_differences():

@@ -2,51 +2,29 @@
 state, branches and mass bookkeeping, fp64 heads and end nodes of the Geff trapezoid, its 119 interior nodes with the fp32
 HARDWARE transcendentals (v_log_f32 / v_exp_f32), summed in fp64.
 
-Against the reference's golden vectors, against the oracle and against the native fp64 kernels.  The bars (derived in
-tests/test_devsim_golden.py and DESIGN.md section 4): front tables 1e-6; per-step outputs within 2e-5 of the water moving
-through the column in that step; run totals 2e-6 of max(|total|, total rainfall); 1e-3 relative on every single per-step
-value as a backstop; IDENTICAL fault flags."""
-import os
-
+Against the reference's golden vectors, against the oracle and against the native fp64 kernels.  The bars (tests/_golden.py,
+derived in DESIGN.md section 4): front tables; per-step outputs against the water moving through the column in that step; run
+totals against max(|total|, total rainfall); a relative backstop on every single per-step value; IDENTICAL fault flags."""
 import numpy as np
 import pytest
 
-from conftest import check_fault_kind, GOLDEN
-from test_devsim_golden import MIXED_FLUX, MIXED_TOTAL, mixed_mode_check
-from test_gpu_parity import TRAJ, _engine, _forcing, _rel
+import _golden as G
+from _golden import MIXED_TOTAL, load, mixed_mode_check, replicated_forcing as _forcing
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 
-@pytest.mark.parametrize("mode", [1, 2], ids=["fast_search", "fast_capacity_chain"])
-@pytest.mark.parametrize("name", TRAJ)
-def test_mixed_precision_trajectory_vs_reference_golden(name, mode):
+def _engine(g, ncol, dtype=torch.float64, **kw):
     import lgar_py_amd as lg
-    g = np.load(os.path.join(GOLDEN, name + ".npz"))
-    ncol = 67
-    crash = int(g["crash_step"])
-    T = crash if crash >= 0 else g["forcing"].shape[0]
-    eng = _engine(g, ncol, torch.float64, search_mode=mode, geff_precision="f32")
-    pr, pe = _forcing(g, ncol, slice(0, T))
-    out = eng.forward(pr, pe, series=lg.ACC_NAMES)
-    got = np.stack([out[nm].cpu().numpy() for nm in lg.ACC_NAMES], 2)  # [T, ncol, NACC]
-    assert (got == got[:, :1]).all(), "replicated columns must be bit-identical"
-    mixed_mode_check(got[:, 0], g["acc"][:T], T)
-    fr = eng.fronts()
-    nf = int(g["nfronts"][T - 1])
-    assert (fr["n_fronts"] == nf).all()
-    assert _rel(fr["depth"][:nf, 0], g["fronts"][T - 1, :nf, 0]).max() <= 1e-6
-    assert _rel(fr["theta"][:nf, 0], g["fronts"][T - 1, :nf, 1]).max() <= 1e-6
-    assert (fr["layer"][:nf, 0] == g["front_layer"][T - 1, :nf]).all()
-    assert (fr["to_bottom"][:nf, 0] == g["front_bottom"][T - 1, :nf]).all()
-    if crash >= 0:
-        pr1, pe1 = _forcing(g, ncol, slice(T, T + 1))
-        with pytest.raises(lg.LgarStatusError):
-            eng.forward(pr1, pe1)
-        assert bool((eng.status != 0).all())
-        check_fault_kind(g, eng.status.cpu().numpy())
+    return lg.LgarEngine(*G.soil(g), n_columns=ncol, dtype=dtype, **G.engine_keywords(g), **kw)
+
+
+@pytest.mark.parametrize("mode", [1, 2], ids=["fast_search", "fast_capacity_chain"])
+@pytest.mark.parametrize("name", G.TRAJ)
+def test_mixed_precision_trajectory_vs_reference_golden(name, mode):
+    G.trajectory_vs_reference(_engine, name, 67, G.check_mixed_trajectory, search_mode=mode, geff_precision="f32")
 
 
 def test_mixed_geff_leaf_on_the_hardware():
@@ -101,12 +79,9 @@ def test_mixed_precision_ensemble_vs_oracle_and_native_fp64():
     pr = f[:, 0:1] * sc[None, :n]
     ro, pc, acc, st = O.run_columns(*(np.ascontiguousarray(P[k][:, :n]) for k in ("alpha", "n", "ksat", "theta_e", "theta_r", "thickness")),
                                     pr, np.zeros_like(pr), pdm=0.0, dt_h=300.0 / 3600.0)
-    assert np.array_equal(st != 0, sm[:n].cpu().numpy() != 0)
-    good = st == 0
-    tot = tm[:8, :n].cpu().numpy()
-    sc8 = np.maximum(np.maximum(np.abs(acc[:8]), acc[0:1]), 1e-2)
-    assert (np.abs(tot - acc[:8]) / sc8)[:, good].max() <= MIXED_TOTAL
-    assert np.abs(rm[:, :n].cpu().numpy() - ro)[:, good].max() <= 2e-4 * np.abs(ro).max()
+    o = dict(ro=ro, acc=acc, st=st)
+    G.check_oracle_agreement(o, sm[:n].cpu().numpy(), totals=tm[:, :n].cpu().numpy(), flips=(), mixed=True)
+    assert np.abs(rm[:, :n].cpu().numpy() - ro)[:, st == 0].max() <= 2e-4 * np.abs(ro).max()
 
 
 def test_mixed_precision_replicas_are_bitwise_equal():
@@ -154,7 +129,7 @@ def test_mixed_giuh_queue_in_place_equals_queue_in_registers(name):
     (the flag "something is queued" is then rebuilt from the loaded rows).  The routed runoff itself is checked against the
     reference's golden series."""
     import lgar_py_amd as lg
-    g = np.load(os.path.join(GOLDEN, name + ".npz"))
+    g = load(name)
     T = g["forcing"].shape[0]
     ncol = 130  # two full waves and a ragged one
     pr, pe = _forcing(g, ncol)

@@ -5,22 +5,11 @@ import os
 import numpy as np
 import pytest
 
+from _model_files import model_cfg as _cfg
 from conftest import GOLDEN
-from test_host_io import write_forcing, write_soil_dat
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-
-
-def _cfg(tmp_path, g, data="Phillipsburg", models="shorter_subcycle", n=300, **over):
-    from lgar_py_amd import config
-    os.makedirs(tmp_path / "data", exist_ok=True)
-    soil = write_soil_dat(str(tmp_path / "data" / "vG_default_params.dat"))
-    step = 60 if models == "shorter_subcycle" else 5
-    forcing = write_forcing(str(tmp_path / "data" / "forcing.csv"), g["forcing"][:n], step_min=step)
-    ov = {"data.forcing_file": forcing, "data.soil_params_file": soil, "models.endtime": n * step / 60.0}
-    ov.update(over)
-    return config.load_config(data=data, models=models, cwd=str(tmp_path), overrides=ov)
 
 
 def test_drop_in_agent_loop_single_column(tmp_path):

@@ -109,9 +109,8 @@ def test_many_fronts_every_step_vs_the_reference_table():
     from the REFERENCE's table of that step.  The project holds every depth and theta of the table to 1e-6 relative
     (test_gpu_parity.py); to first order that moves a bin's storage by at most 1e-6 * sum_j theta_j (|w_j| + |d_j| + |t_j|)
     (clip is 1-Lipschitz; 1.01 covers the second order), and its mean theta by that over the bin's in-column width."""
-    from test_moisture_host import tables
     g, eng, pr, pe = _replicated("manyfronts_pulse_84", 3, torch.float64, search_mode=2, front_slots=32)
-    t = tables("manyfronts_pulse_84")
+    t = MH.tables("manyfronts_pulse_84")
     args = (t["depth"], t["theta"], t["layer"], t["n_fronts"], t["thickness"])
     T = pr.shape[0]
     assert int(t["n_fronts"].max()) == 31
@@ -286,7 +285,7 @@ def test_model_surface(tmp_path):
     Phillipsburg configuration; the layers' storage sums to the model's ending_volume."""
     from lgar_py_amd.data import Data
     from lgar_py_amd.model import dpLGAR
-    from test_gpu_model import _cfg
+    from _model_files import model_cfg as _cfg
     g = np.load(os.path.join(GOLDEN, "phil_hourly_3000.npz"))
     cfg = _cfg(tmp_path, g, n=40)
     data = Data(cfg)

@@ -1,134 +1,65 @@
 """GPU (-m gpu): the HIP path, called through the C-ABI, against the golden vectors captured from the
 reference and against the CPU oracle on the same seeded inputs.
 
-Tolerances: fp64 1e-6 relative per step on every accumulator (north_star; observed <= 1e-9);
+Bars and checks: tests/_golden.py (observed in fp64: <= 1e-9 relative per step on every accumulator);
 fp32 (the throughput configuration) 5e-3 relative on run totals (99th percentile of columns) -- fp32 cannot hold the reference's
 absolute 1e-12 mass tolerance, see DESIGN.md."""
-import os
-
 import numpy as np
 import pytest
 
-from _golden import engine_keywords
-from conftest import check_fault_kind, GOLDEN, golden_names
+import _golden as G
+from _golden import load, rel as _rel, replicated_forcing as _forcing, to_numpy as _np
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-
-def _rel(a, b, floor=1e-6):
-    return np.abs(a - b) / np.maximum(np.abs(b), floor)
+LANES_STATE = ("depth", "theta", "psi", "k", "dzdt", "flags", "n_fronts", "status", "scalars", "totals")
 
 
-def _engine(g, ncol, dtype, **kw):
+def _engine(g, ncol, dtype=torch.float64, **kw):
     import lgar_py_amd as lg
-    return lg.LgarEngine(g["alpha"], g["n"], g["ksat"], g["theta_e"], g["theta_r"], g["thickness"], n_columns=ncol,
-                         dtype=dtype, **engine_keywords(g), **kw)
+    return lg.LgarEngine(*G.soil(g), n_columns=ncol, dtype=dtype, **G.engine_keywords(g), **kw)
 
 
-def _forcing(g, ncol, sl=slice(None)):
-    f = torch.tensor(g["forcing"][sl])
-    T = f.shape[0]
-    return f[:, 0:1].expand(T, ncol).contiguous(), f[:, 1:2].expand(T, ncol).contiguous()
-
-
-TRAJ = [n for n in golden_names() if not n.startswith("grad_")]
+def _oracle_engine(o, **kw):
+    import lgar_py_amd as lg
+    return lg.LgarEngine(*o["cols"], **o["kw"], **dict(dict(dtype=torch.float64), **kw))
 
 
 @pytest.mark.parametrize("mode", [1, 2, 0], ids=["fast_search", "fast_capacity_chain", "literal_search"])
-@pytest.mark.parametrize("name", TRAJ)
+@pytest.mark.parametrize("name", G.TRAJ)
 def test_fp64_trajectory_vs_reference_golden(name, mode):
     """All search modes against the reference: 0 = its literal fixed-step line searches (and trapezoid), 1 (the default,
     what bench.py measures) = Newton / closed-form-jump searches to the same tolerances, 2 = 1 with the front-capacity
     chain (8 -> 16 -> 32 slots) forced for this small job."""
-    import lgar_py_amd as lg
-    g = np.load(os.path.join(GOLDEN, name + ".npz"))
-    ncol = 67  # one full wave + a ragged tail
-    crash = int(g["crash_step"])
-    T = crash if crash >= 0 else g["forcing"].shape[0]
-    eng = _engine(g, ncol, torch.float64, search_mode=mode)
-    assert abs(float(eng.ending_volume[0]) - float(g["init_volume"])) <= 1e-9
-    pr, pe = _forcing(g, ncol, slice(0, T))
-    out = eng.forward(pr, pe, series=lg.ACC_NAMES)
-    for j, nm in enumerate(lg.ACC_NAMES):
-        got = out[nm].cpu().numpy()
-        assert _rel(got[:, 0], g["acc"][:T, j]).max() <= 1e-6, nm
-        assert (got == got[:, :1]).all(), "replicated columns must be bit-identical"
-    fr = eng.fronts()
-    nf = int(g["nfronts"][T - 1])
-    assert (fr["n_fronts"] == nf).all()
-    assert _rel(fr["depth"][:nf, 0], g["fronts"][T - 1, :nf, 0]).max() <= 1e-6
-    assert _rel(fr["theta"][:nf, 0], g["fronts"][T - 1, :nf, 1]).max() <= 1e-6
-    assert _rel(fr["psi"][:nf, 0], g["fronts"][T - 1, :nf, 2], 1e-3).max() <= 1e-5
-    assert _rel(fr["k"][:nf, 0], g["fronts"][T - 1, :nf, 3], 1e-12).max() <= 1e-5   # K(theta), deepest front keeps its initial K
-    assert _rel(fr["dzdt"][:nf, 0], g["fronts"][T - 1, :nf, 4], 1e-9).max() <= 1e-5
-    assert (fr["layer"][:nf, 0] == g["front_layer"][T - 1, :nf]).all()
-    assert (fr["to_bottom"][:nf, 0] == g["front_bottom"][T - 1, :nf]).all()
-    # run totals (what MassBalance accumulates)
-    for j in range(8):
-        assert _rel(float(eng.totals[j, 0]), g["acc"][:T, j].sum()) <= 1e-6
-    if crash >= 0:
-        # the reference raised at this step (ValueError / AttributeError): every column must fault here too
-        pr1, pe1 = _forcing(g, ncol, slice(T, T + 1))
-        with pytest.raises(lg.LgarStatusError):
-            eng.forward(pr1, pe1)
-        assert bool((eng.status != 0).all())
-        check_fault_kind(g, eng.status.cpu().numpy())
+    G.trajectory_vs_reference(_engine, name, 67, G.check_native_trajectory, search_mode=mode)  # one full wave + a ragged tail
 
 
-# engine settings per mode and the bar on depth / theta (relative to the reference's own value); "fast" lets the library choose
-# its kernel for a job this small (cooperating lanes), "fast_capacity_chain" forces the one-lane-per-column kernels of the big jobs
-# The mixed-precision mode holds 1e-6 except in the step of a front event, where a random 1e-7 difference between consecutive
-# Geff values is amplified ~50x: every step within 2e-5 -- the mode's bar on per-step fluxes -- and all but
-# 2 % of the steps within 2e-6.
-STEPWISE_MODES = {"fast": (dict(search_mode=1), 1e-6, 1e-6), "fast_capacity_chain": (dict(search_mode=2), 1e-6, 1e-6),
-                  "literal": (dict(search_mode=0), 1e-7, 1e-7), "mixed": (dict(search_mode=2, geff_precision="f32"), 2e-5, 2e-6),
-                  "mixed_cooperating_lanes": (dict(search_mode=1, geff_precision="f32"), 2e-5, 2e-6)}
+# engine settings per mode; (bar, usual) from _golden.py.  "fast" lets the library choose its kernel for a job this small
+# (cooperating lanes), "fast_capacity_chain" forces the one-lane-per-column kernels of the big jobs
+STEPWISE_MODES = {"fast": (dict(search_mode=1), G.STEPWISE_NATIVE), "fast_capacity_chain": (dict(search_mode=2), G.STEPWISE_NATIVE),
+                  "literal": (dict(search_mode=0), G.STEPWISE_LITERAL),
+                  "mixed": (dict(search_mode=2, geff_precision="f32"), G.STEPWISE_MIXED_GPU),
+                  "mixed_cooperating_lanes": (dict(search_mode=1, geff_precision="f32"), G.STEPWISE_MIXED_GPU)}
 
 
 @pytest.mark.parametrize("mode", list(STEPWISE_MODES))
-@pytest.mark.parametrize("name", TRAJ)
+@pytest.mark.parametrize("name", G.TRAJ)
 def test_fp64_front_table_at_every_step_vs_reference_golden(name, mode):
     """north_star: "per-front depth/theta".  The HIP engine is stepped one forcing row at a time through the C-ABI and its WHOLE
     front table -- front count, layer tags, to_bottom flags, depth, theta (layers/WettingFront.py:38-49,
     models/dpLGAR.py:176-298) -- is compared with the reference's at EVERY step, not only at the last one."""
-    kw, bar, usual = STEPWISE_MODES[mode]
-    g = np.load(os.path.join(GOLDEN, name + ".npz"))
-    crash = int(g["crash_step"])
-    T = crash if crash >= 0 else g["forcing"].shape[0]
-    if mode == "literal" and T > 600:
-        T = 600  # (the literal line searches take ~100x the evaluations: the head of the long fixtures)
-    ncol = 2
-    eng = _engine(g, ncol, torch.float64, **kw)
-    pr, pe = _forcing(g, ncol, slice(0, T))
-    F = eng.depth.shape[0]
-    dev = eng.depth.device
-    Z = torch.empty(T, F, dtype=torch.float64, device=dev)
-    TH = torch.empty(T, F, dtype=torch.float64, device=dev)
-    FL = torch.empty(T, F, dtype=torch.uint8, device=dev)
-    NF = torch.empty(T, dtype=torch.int32, device=dev)
-    for t in range(T):
-        eng.forward(pr[t:t + 1], pe[t:t + 1], series=(), check=False)
-        Z[t], TH[t], FL[t], NF[t] = eng.depth[:, 0], eng.theta[:, 0], eng.flags[:, 0], eng.n_fronts[0]
-    assert bool((eng.status == 0).all())
-    assert torch.equal(eng.depth[:, 0], eng.depth[:, 1]) and torch.equal(eng.theta[:, 0], eng.theta[:, 1])
-    Z, TH, FL, NF = Z.cpu().numpy(), TH.cpu().numpy(), FL.cpu().numpy(), NF.cpu().numpy()
-    assert (NF == g["nfronts"][:T]).all(), int(np.argmax(NF != g["nfronts"][:T]))
-    frec = min(g["fronts"].shape[1], F)
-    live = np.arange(frec)[None, :] < np.minimum(NF, frec)[:, None]
-    assert ((FL[:, :frec] & 0x7F)[live] == g["front_layer"][:T, :frec][live]).all()
-    assert ((FL[:, :frec] >> 7)[live] == g["front_bottom"][:T, :frec][live]).all()
-    err = np.maximum(_rel(Z[:, :frec], g["fronts"][:T, :frec, 0]), _rel(TH[:, :frec], g["fronts"][:T, :frec, 1]))
-    err = np.where(live, err, 0.0).max(axis=1)  # worst front of every step
-    assert err.max() <= bar, (int(err.argmax()), float(err.max()))
-    assert int((err > usual).sum()) <= max(1, T // 50), (int((err > usual).sum()), T, float(err.max()))
+    kw, (bar, usual) = STEPWISE_MODES[mode]
+    g = load(name)
+    T = G.steps_before_crash(g, G.STEPWISE_LITERAL_STEPS if mode == "literal" else None)[1]
+    G.check_front_table_at_every_step(g, G.run_row_by_row(_engine, g, 2, T, **kw), T, bar, usual)
 
 
 def test_config2_10k_replicated_phillipsburg_fp64():
     """BASELINE configs[1]: 10k replicated Phillipsburg columns, fp64, every column == reference to 1e-6 rel."""
     import lgar_py_amd as lg
-    g = np.load(os.path.join(GOLDEN, "phil_hourly_3000.npz"))
+    g = load("phil_hourly_3000")
     N = 10_000
     eng = _engine(g, N, torch.float64)
     pr, pe = _forcing(g, N)
@@ -136,21 +67,21 @@ def test_config2_10k_replicated_phillipsburg_fp64():
     for nm in out:
         got = out[nm]
         ref = torch.tensor(g["acc"][:, lg.ACC_NAMES.index(nm)], device=got.device)[:, None]
-        rel = ((got - ref).abs() / ref.abs().clamp_min(1e-6)).max().item()
-        assert rel <= 1e-6, (nm, rel)
+        rel = ((got - ref).abs() / ref.abs().clamp_min(G.REL_FLOOR)).max().item()
+        assert rel <= G.NATIVE, (nm, rel)
     cum = out["infiltration"].sum(0)
     assert abs(float(cum[0]) - 19.786600000000007) <= 1e-6 * 19.8
     assert float((cum - cum[0]).abs().max()) == 0.0
     fr = eng.fronts()
     nf = int(g["nfronts"][-1])
     assert (fr["n_fronts"] == nf).all()
-    assert _rel(fr["depth"][:nf], g["fronts"][-1, :nf, 0:1]).max() <= 1e-6
-    assert _rel(fr["theta"][:nf], g["fronts"][-1, :nf, 1:2]).max() <= 1e-6
+    assert _rel(fr["depth"][:nf], g["fronts"][-1, :nf, 0:1]).max() <= G.NATIVE
+    assert _rel(fr["theta"][:nf], g["fronts"][-1, :nf, 1:2]).max() <= G.NATIVE
 
 
 def test_chunked_run_equals_single_run():
     """State persistence across calls: T steps in one launch == the same T steps in ragged chunks (bitwise)."""
-    g = np.load(os.path.join(GOLDEN, "synth0_phil_1500.npz"))
+    g = load("synth0_phil_1500")
     ncol = 3
     pr, pe = _forcing(g, ncol, slice(0, 300))
     a = _engine(g, ncol, torch.float64)
@@ -175,32 +106,19 @@ def test_heterogeneous_columns_vs_oracle_fp64():
     """Seeded +-10 % perturbed columns with per-column forcing scale (the bench workload's shape at a size the
     oracle finishes in seconds): every column within 1e-6 rel of the oracle; mass closes per column."""
     import lgar_py_amd as lg
-    from lgar_py_amd import workloads as W
-    from oracle import lgar_oracle as O
-    N = 512
-    P = W.perturbed_columns(N, seed=7)
-    sc = W.forcing_scale(N, seed=8)
-    f = W.synth1_forcing()
-    pr = f[:, 0:1] * sc[None, :]
-    pe = np.zeros_like(pr)
-    ro, pc, acc, st = O.run_columns(P["alpha"], P["n"], P["ksat"], P["theta_e"], P["theta_r"], P["thickness"], pr, pe,
-                                    pdm=0.0, dt_h=300.0 / 3600.0)
+    o = G.oracle_ensemble(512, seed=7, scale=(8,))
+    st, acc = o["st"], o["acc"]
     for mode in (0, 1, 2):  # literal searches; the default fast mode bench.py times; fast with the capacity chain
-        eng = lg.LgarEngine(P["alpha"], P["n"], P["ksat"], P["theta_e"], P["theta_r"], P["thickness"], dt_h=300.0 / 3600.0,
-                            ponded_depth_max=0.0, dtype=torch.float64, search_mode=mode)
+        eng = _oracle_engine(o, search_mode=mode)
         v0 = eng.ending_volume.clone()
-        out = eng.forward(torch.tensor(pr), torch.tensor(pe), series=("runoff", "percolation"), check=False)
+        out = eng.forward(torch.tensor(o["pr"]), torch.tensor(o["pe"]), series=("runoff", "percolation"), check=False)
         # Some perturbed columns leave the reference's domain of validity (it raises ValueError: negative pow base in
         # insert_water's Geff, quirk q3); oracle and kernel must flag exactly the same columns, and still agree on them.
-        gst = eng.status.cpu().numpy()
-        assert ((st != 0) == (gst != 0)).all(), mode
         assert 0 < (st != 0).mean() < 0.5
         with pytest.raises(lg.LgarStatusError):
             eng.check_status()
-        got = out["runoff"].cpu().numpy()
-        assert np.abs(got - ro).max() <= 1e-6 * max(1.0, np.abs(ro).max()), mode
-        tot = eng.totals.cpu().numpy()
-        assert _rel(tot[:8], acc[:8], 1e-3).max() <= 1e-6, mode
+        tot = _np(eng.totals)
+        G.check_oracle_agreement(o, _np(eng.status), _np(out["runoff"]), tot, flips=(), cols=slice(None))
         assert _rel(tot[9], acc[9]).max() <= 1e-9
         # size-independent property: the global mass balance of MassBalance.report_mass (MassBalance.py:84-92) closes
         # for the bulk of the columns.  It is NOT an invariant of the reference's algorithm (its own synth3 run with
@@ -213,20 +131,10 @@ def test_heterogeneous_columns_vs_oracle_fp64():
 def test_fp32_throughput_configuration_vs_oracle():
     """fp32 (BASELINE configs[2]) against the fp64 oracle on the same seeded columns: run totals within 5e-3
     relative (99th percentile; 5e-2 worst column), basin runoff within 1e-3, no faulted column."""
-    import lgar_py_amd as lg
-    from lgar_py_amd import workloads as W
-    from oracle import lgar_oracle as O
-    N = 1024
-    P = W.perturbed_columns(N, seed=0)
-    sc = W.forcing_scale(N, seed=1)
-    f = W.synth1_forcing()
-    pr = f[:, 0:1] * sc[None, :]
-    pe = np.zeros_like(pr)
-    ro, pc, acc, st = O.run_columns(P["alpha"], P["n"], P["ksat"], P["theta_e"], P["theta_r"], P["thickness"], pr, pe,
-                                    pdm=0.0, dt_h=300.0 / 3600.0)
-    eng = lg.LgarEngine(P["alpha"], P["n"], P["ksat"], P["theta_e"], P["theta_r"], P["thickness"], dt_h=300.0 / 3600.0,
-                        ponded_depth_max=0.0, dtype=torch.float32)
-    out = eng.forward(torch.tensor(pr), torch.tensor(pe), series=("runoff",), check=False)
+    o = G.oracle_ensemble(1024, seed=0, scale=(1,))
+    ro, acc, st = o["ro"], o["acc"], o["st"]
+    eng = _oracle_engine(o, dtype=torch.float32)
+    out = eng.forward(torch.tensor(o["pr"]), torch.tensor(o["pe"]), series=("runoff",), check=False)
     gst = eng.status.cpu().numpy()
     # Which columns leave the reference's domain of validity hinges on a psi tie at the 1e-8 level (free-drainage
     # front choice right after a layer crossing), so the fp32 and fp64 sets differ; compare where both are valid.
@@ -246,7 +154,7 @@ def test_fp32_throughput_configuration_vs_oracle():
 
 def test_leaf_kats_on_gpu():
     import lgar_py_amd as lg
-    g = np.load(os.path.join(GOLDEN, "leaf_kats.npz"))
+    g = load("leaf_kats")
     soils = g["soils"]
     S = len(soils)
 
@@ -288,7 +196,7 @@ def test_domain_bottom_raises_like_reference():
     """A front reaching the domain bottom kills the reference (AttributeError, Layer.py:980); here the column's
     status gets LGAR_ST_BOTTOM and the wrapper raises a ValueError subclass."""
     import lgar_py_amd as lg
-    g = np.load(os.path.join(GOLDEN, "synth1_phil.npz"))
+    g = load("synth1_phil")
     eng = lg.LgarEngine(g["alpha"], g["n"], g["ksat"], g["theta_e"], g["theta_r"], [4.0, 4.0, 4.0], n_columns=5,
                         dt_h=float(g["dt_h"]), ponded_depth_max=0.0)
     pr, pe = _forcing(g, 5)
@@ -308,7 +216,7 @@ def test_bad_arguments_are_rejected():
         lg.LgarEngine([1e-2] * 3, [1.0, 1.5, 1.5], [1.0] * 3, [0.4] * 3, [0.1] * 3, [10.0] * 3, n_columns=4)
     with pytest.raises(lg.LgarError, match="theta_e > theta_r"):
         lg.LgarEngine([1e-2] * 3, [1.5] * 3, [1.0] * 3, [0.4, 0.05, 0.4], [0.1] * 3, [10.0] * 3, n_columns=4)
-    g = np.load(os.path.join(GOLDEN, "synth1_phil.npz"))
+    g = load("synth1_phil")
     eng = _engine(g, 4, torch.float64)
     with pytest.raises(lg.LgarError):
         eng.forward(torch.zeros(3, 5), torch.zeros(3, 5))  # wrong column count
@@ -331,7 +239,7 @@ def test_bad_arguments_are_rejected():
 def test_nan_in_the_forcing_is_flagged_on_gpu():
     """A NaN forcing value slips through the reference silently; the engine flags that column and only that column."""
     import lgar_py_amd as lg
-    g = np.load(os.path.join(GOLDEN, "synth1_phil.npz"))
+    g = load("synth1_phil")
     for dtype in (torch.float64, torch.float32):
         eng = _engine(g, 130, dtype)
         pr, pe = _forcing(g, 130)
@@ -347,29 +255,16 @@ def test_nan_in_the_forcing_is_flagged_on_gpu():
 def test_heterogeneous_hourly_with_pet_vs_oracle_fp64():
     """Perturbed columns under the hourly Phillipsburg forcing (rain + PET: AET, dry-over-wet, merges, base case)
     scaled per column: kernel (literal searches) vs oracle column by column, 600 steps."""
-    import lgar_py_amd as lg
-    from lgar_py_amd import workloads as W
-    from oracle import lgar_oracle as O
-    g = np.load(os.path.join(GOLDEN, "phil_hourly_3000.npz"))
-    N, T = 256, 600
-    P = W.perturbed_columns(N, seed=21)
-    sc = W.forcing_scale(N, 0.5, 2.0, seed=22)
-    pr = g["forcing"][:T, 0:1] * sc[None, :]
-    pe = g["forcing"][:T, 1:2] * np.ones((1, N))
-    ro, pc, acc, st = O.run_columns(P["alpha"], P["n"], P["ksat"], P["theta_e"], P["theta_r"], P["thickness"], pr, pe,
-                                    pdm=2.0, dt_h=1.0)
-    for mode, tol in ((0, 1e-6), (1, 1e-6)):
-        eng = lg.LgarEngine(P["alpha"], P["n"], P["ksat"], P["theta_e"], P["theta_r"], P["thickness"], dt_h=1.0,
-                            ponded_depth_max=2.0, dtype=torch.float64, search_mode=mode)
-        out = eng.forward(torch.tensor(pr), torch.tensor(pe), series=("runoff", "AET", "infiltration"), check=False)
-        gst = eng.status.cpu().numpy()
-        if mode == 0:
-            assert ((st != 0) == (gst != 0)).all()
-        ok = (st == 0) & (gst == 0)
+    o = G.oracle_ensemble(256, seed=21, scale=(0.5, 2.0, 22), hourly_steps=600)
+    st, acc = o["st"], o["acc"]
+    for mode in (0, 1):
+        eng = _oracle_engine(o, search_mode=mode)
+        eng.forward(torch.tensor(o["pr"]), torch.tensor(o["pe"]), series=("runoff", "AET", "infiltration"), check=False)
+        ok = (st == 0) & (_np(eng.status) == 0)
         assert ok.mean() > 0.9
-        tot = eng.totals.cpu().numpy()
-        assert _rel(tot[:8, ok], acc[:8, ok], 1e-3).max() <= tol, mode
-        assert _rel(tot[9, ok], acc[9, ok]).max() <= tol
+        tot = _np(eng.totals)
+        G.check_oracle_agreement(o, _np(eng.status), None, tot, flips=() if mode == 0 else None, cols=ok)
+        assert _rel(tot[9, ok], acc[9, ok]).max() <= G.NATIVE
         assert tot[2, ok].min() > 0  # AET path exercised
         fr = eng.fronts()
         assert fr["n_fronts"][ok].max() <= 12
@@ -380,28 +275,12 @@ def test_wet_hourly_ensemble_faults_where_the_oracle_does():
     shape): a few columns hit the reference's ValueError inside fix_dry_over_wet (psi of another layer's theta, Se > 1,
     Layer.py:1117-1143; fixture crash_dry_over_wet_300 is the reference's own run of one of them) -- a NaN that update_psi
     overwrites before anything reads it.  Every mode must flag exactly the oracle's columns and agree to 1e-6 elsewhere."""
-    import lgar_py_amd as lg
-    from lgar_py_amd import workloads as W
-    from oracle import lgar_oracle as O
-    g = np.load(os.path.join(GOLDEN, "phil_hourly_3000.npz"))
-    N, T = 4096, 600
-    P = W.perturbed_columns(N, seed=400)
-    sc = W.forcing_scale(N, 0.5, 3.0, seed=500)
-    pr = g["forcing"][:T, 0:1] * sc[None, :]
-    pe = g["forcing"][:T, 1:2] * np.ones((1, N))
-    ro, pc, acc, st = O.run_columns(P["alpha"], P["n"], P["ksat"], P["theta_e"], P["theta_r"], P["thickness"], pr, pe,
-                                    pdm=2.0, dt_h=1.0)
-    assert st[1270] != 0 and 0 < (st != 0).sum() < 100
+    o = G.oracle_ensemble(4096, seed=400, scale=(0.5, 3.0, 500), hourly_steps=600)
+    assert o["st"][1270] != 0 and 0 < (o["st"] != 0).sum() < 100
     for mode in (0, 1, 2):
-        eng = lg.LgarEngine(P["alpha"], P["n"], P["ksat"], P["theta_e"], P["theta_r"], P["thickness"], dt_h=1.0,
-                            ponded_depth_max=2.0, dtype=torch.float64, search_mode=mode)
-        out = eng.forward(torch.tensor(pr), torch.tensor(pe), series=("runoff",), check=False)
-        gst = eng.status.cpu().numpy()
-        assert ((st != 0) == (gst != 0)).all(), mode
-        ok = st == 0
-        assert np.abs(out["runoff"].cpu().numpy() - ro)[:, ok].max() <= 1e-6 * max(1.0, np.abs(ro).max()), mode
-        tot = eng.totals.cpu().numpy()
-        assert _rel(tot[:8, ok], acc[:8, ok], 1e-3).max() <= 1e-6, mode
+        eng = _oracle_engine(o, search_mode=mode)
+        out = eng.forward(torch.tensor(o["pr"]), torch.tensor(o["pe"]), series=("runoff",), check=False)
+        G.check_oracle_agreement(o, _np(eng.status), _np(out["runoff"]), _np(eng.totals), flips=())
 
 
 # columns of W.ensemble_columns(512, seed=3) on which kernel and oracle may disagree about a fault, per search mode
@@ -411,33 +290,17 @@ WIDE_ENSEMBLE_BORDERLINE = {0: set(), 1: set()}
 def test_wide_parameter_ensemble_vs_oracle_fp64():
     """BASELINE configs[4]'s parameter ranges (alpha in [0.0015, 0.015], n in [1.1, 3], Ksat in [0.01, 5]) under the
     synth_1 storm: kernel vs oracle per column; the same columns leave the reference's domain of validity."""
-    import lgar_py_amd as lg
-    from lgar_py_amd import workloads as W
-    from oracle import lgar_oracle as O
-    N = 512
-    E = W.ensemble_columns(N, seed=3)
-    f = W.synth1_forcing()
-    pr = np.repeat(f[:, 0:1], N, 1)
-    pe = np.zeros_like(pr)
-    ro, pc, acc, st = O.run_columns(E["alpha"], E["n"], E["ksat"], E["theta_e"], E["theta_r"], E["thickness"], pr, pe,
-                                    pdm=0.0, dt_h=300.0 / 3600.0)
+    o = G.oracle_ensemble(512, seed=3, wide=True)
     for mode in (0, 1):
-        eng = lg.LgarEngine(E["alpha"], E["n"], E["ksat"], E["theta_e"], E["theta_r"], E["thickness"], dt_h=300.0 / 3600.0,
-                            ponded_depth_max=0.0, dtype=torch.float64, search_mode=mode)
-        out = eng.forward(torch.tensor(pr), torch.tensor(pe), series=("runoff",), check=False)
-        gst = eng.status.cpu().numpy()
-        agree = ((st != 0) == (gst != 0))
+        eng = _oracle_engine(o, search_mode=mode)
+        out = eng.forward(torch.tensor(o["pr"]), torch.tensor(o["pe"]), series=("runoff",), check=False)
         # Exact agreement is the rule.  The only disagreements admitted are the columns NAMED here: ones whose top layer
         # saturates (psi -> 0), where the reference's own decision (an isclose tie at 1e-8, the Se > 1 fault of insert_water)
         # hinges on the last bit of pow -- device vs glibc (DESIGN.md section 4).  A new disagreement fails the test.
-        flipped = set(int(i) for i in np.nonzero(~agree)[0])
-        assert flipped <= WIDE_ENSEMBLE_BORDERLINE[mode], (mode, sorted(flipped))
-        ok = (st == 0) & (gst == 0)
+        ok = (o["st"] == 0) & (_np(eng.status) == 0)
         assert ok.mean() > 0.5
-        tot = eng.totals.cpu().numpy()
-        assert _rel(tot[:8, ok], acc[:8, ok], 1e-3).max() <= 1e-6, mode
-        got = out["runoff"].cpu().numpy()
-        assert np.abs(got[:, ok] - ro[:, ok]).max() <= 1e-6 * max(1.0, np.abs(ro[:, ok]).max()), mode
+        G.check_oracle_agreement(o, _np(eng.status), _np(out["runoff"]), _np(eng.totals), flips=WIDE_ENSEMBLE_BORDERLINE[mode],
+                                 cols=ok, scale=max(1.0, np.abs(o["ro"][:, ok]).max()))
 
 
 @pytest.mark.timeout(900)
@@ -448,23 +311,15 @@ def test_wide_parameter_sweep_65536_columns_vs_oracle():
     other libm: the count is bounded (<= 0.05 % fault-flag flips, <= 0.05 % of the jointly valid columns off by more than
     1e-6; observed r03: 0.016-0.026 % in total), everything else agrees to 1e-6.  The mixed-precision mode is held to its own,
     wider bar on this ill-conditioned ensemble (<= 0.4 % flips)."""
-    import lgar_py_amd as lg
-    from lgar_py_amd import workloads as W
-    from oracle import lgar_oracle as O
     N = 65536
-    E = W.ensemble_columns(N, seed=300)
-    f = W.synth1_forcing()
-    pr = np.repeat(f[:, 0:1], N, 1)
-    pe = np.zeros_like(pr)
-    ro, pc, acc, st = O.run_columns(E["alpha"], E["n"], E["ksat"], E["theta_e"], E["theta_r"], E["thickness"], pr, pe,
-                                    pdm=0.0, dt_h=300.0 / 3600.0)
+    o = G.oracle_ensemble(N, seed=300, wide=True)
+    ro, st = o["ro"], o["st"]
     scale = max(1.0, np.abs(ro).max())
     report = {}
     for mode in (1, 0, "mixed"):
         mk = dict(search_mode=1, geff_precision="f32") if mode == "mixed" else dict(search_mode=mode)
-        eng = lg.LgarEngine(E["alpha"], E["n"], E["ksat"], E["theta_e"], E["theta_r"], E["thickness"], dt_h=300.0 / 3600.0,
-                            ponded_depth_max=0.0, dtype=torch.float64, **mk)
-        out = eng.forward(torch.tensor(pr), torch.tensor(pe), series=("runoff",), check=False)
+        eng = _oracle_engine(o, **mk)
+        out = eng.forward(torch.tensor(o["pr"]), torch.tensor(o["pe"]), series=("runoff",), check=False)
         gst = eng.status.cpu().numpy() & 0x7f
         flips = int(((st != 0) != (gst != 0)).sum())
         both = (st == 0) & (gst == 0)
@@ -484,7 +339,7 @@ def test_percolating_bottom_boundary_matches_oracle():
     reach the domain bottom leave as percolation and the column keeps integrating."""
     import lgar_py_amd as lg
     from oracle import lgar_oracle as O
-    g = np.load(os.path.join(GOLDEN, "synth1_phil.npz"))
+    g = load("synth1_phil")
     thick = [4.0, 4.0, 4.0]
     p = O.make_params(g["alpha"], g["n"], g["ksat"], g["theta_e"], g["theta_r"], thick, pdm=0.0, dt_h=float(g["dt_h"]))
     p.bottom_mode = 1
@@ -500,7 +355,7 @@ def test_percolating_bottom_boundary_matches_oracle():
         out = eng.forward(pr, pe, series=lg.ACC_NAMES)
         for j, nm in enumerate(lg.ACC_NAMES):
             got = out[nm][:, 0].cpu().numpy()
-            assert np.abs(got - ref["acc"][:, j]).max() <= 1e-6 * max(1.0, np.abs(ref["acc"][:, j]).max()), (mode, nm)
+            assert np.abs(got - ref["acc"][:, j]).max() <= G.NATIVE * max(1.0, np.abs(ref["acc"][:, j]).max()), (mode, nm)
         t = eng.totals[:, 0].cpu().numpy()
         assert abs(t[5] - ref["acc"][:, 5].sum()) <= 1e-9 and t[5] > 0.05
         # (this 12 cm toy column does not close its balance exactly: the reference clamps layer-0 fronts to the column
@@ -516,7 +371,7 @@ def test_capacity_chain_on_gpu_many_fronts():
     fronts, every 97th one grows to 31 (the reference's own trajectory, manyfronts_pulse_84) and moves through the 16- and
     32-slot kernels inside the same call; one more pulse series drives those past 32 -> LGAR_ST_OVERFLOW only there."""
     import lgar_py_amd as lg
-    g = np.load(os.path.join(GOLDEN, "manyfronts_pulse_84.npz"))
+    g = load("manyfronts_pulse_84")
     N = 70_000
     T = g["forcing"].shape[0]
     scale = torch.zeros(N, dtype=torch.float64)
@@ -530,13 +385,13 @@ def test_capacity_chain_on_gpu_many_fronts():
     for nm in ("runoff", "infiltration", "ending_volume"):
         ref = g["acc"][:, lg.ACC_NAMES.index(nm)]
         got = out[nm][:, big].cpu().numpy()
-        assert _rel(got, ref[:, None]).max() <= 1e-6, nm
+        assert _rel(got, ref[:, None]).max() <= G.NATIVE, nm
         assert (got == got[:, :1]).all()
     assert np.allclose(out["basin:runoff"].cpu().numpy(), g["acc"][:, 4] * len(big), rtol=1e-9, atol=1e-12)
     fr = eng.fronts()
     c = int(big[5])
-    assert _rel(fr["depth"][:31, c], g["fronts"][T - 1, :31, 0]).max() <= 1e-6
-    assert _rel(fr["theta"][:31, c], g["fronts"][T - 1, :31, 1]).max() <= 1e-6
+    assert _rel(fr["depth"][:31, c], g["fronts"][T - 1, :31, 0]).max() <= G.NATIVE
+    assert _rel(fr["theta"][:31, c], g["fronts"][T - 1, :31, 1]).max() <= G.NATIVE
     more = torch.tensor(np.tile([0.02, 0.0], 30)[:, None]) * scale[None, :]
     with pytest.raises(lg.LgarStatusError, match="front overflow"):
         eng.forward(more, torch.zeros_like(more))
@@ -556,7 +411,7 @@ def test_single_step_transitions_from_injected_reference_states(name):
     reference's next step.  Covers create / insert_water / in-layer moves / base case / merge / layer crossing /
     dry-over-wet as (state_in, forcing) -> state_out pairs, and the HBM -> LDS state load path."""
     import lgar_py_amd as lg
-    g = np.load(os.path.join(GOLDEN, name + ".npz"))
+    g = load(name)
     nf = g["nfronts"]
     T = len(nf)
     ks = sorted(set([k for k in range(T - 1) if nf[k + 1] != nf[k]] + list(range(0, T - 1, 17))))
@@ -582,13 +437,13 @@ def test_single_step_transitions_from_injected_reference_states(name):
     out = eng.forward(pr, pe, series=lg.ACC_NAMES)
     for j, nm in enumerate(lg.ACC_NAMES):
         got = out[nm][0].cpu().numpy()
-        assert _rel(got, g["acc"][nxt, j]).max() <= 1e-6, nm
+        assert _rel(got, g["acc"][nxt, j]).max() <= G.NATIVE, nm
     res = eng.fronts()
     assert (res["n_fronts"] == nf[nxt]).all()
     for c, k in enumerate(nxt):
         n = int(nf[k])
-        assert _rel(res["depth"][:n, c], g["fronts"][k, :n, 0]).max() <= 1e-6, k
-        assert _rel(res["theta"][:n, c], g["fronts"][k, :n, 1]).max() <= 1e-6, k
+        assert _rel(res["depth"][:n, c], g["fronts"][k, :n, 0]).max() <= G.NATIVE, k
+        assert _rel(res["theta"][:n, c], g["fronts"][k, :n, 1]).max() <= G.NATIVE, k
         assert (res["layer"][:n, c] == g["front_layer"][k, :n]).all() and (res["to_bottom"][:n, c] == g["front_bottom"][k, :n]).all()
 
 
@@ -600,22 +455,7 @@ def test_cooperating_lanes_reproduce_one_lane_per_column(name, lanes):
     left-over lanes join the last group) that split the Geff trapezoid's nodes (and the pows that open it) between them, with
     one front table per group of lanes.  Every per-step output, the final front tables and the run totals are those of one
     lane per column BIT FOR BIT."""
-    import lgar_py_amd as lg
-    g = np.load(os.path.join(GOLDEN, name + ".npz"))
-    ncol = 5
-    res = {}
-    for k in (1, lanes):
-        eng = _engine(g, ncol, torch.float64, forward_lanes=k)
-        pr, pe = _forcing(g, ncol)
-        out = eng.forward(pr, pe, series=lg.ACC_NAMES, check=False)
-        res[k] = (out, eng)
-    a, ea = res[1]
-    b, eb = res[lanes]
-    for nm in lg.ACC_NAMES:
-        assert torch.equal(a[nm], b[nm]), nm
-    for t in ("depth", "theta", "psi", "k", "dzdt", "flags", "n_fronts", "status", "scalars"):
-        assert torch.equal(getattr(ea, t), getattr(eb, t)), t
-    assert torch.equal(ea.totals, eb.totals)
+    G.check_bit_identical(*G.run_lanes_pair(_engine, load(name), 5, lanes, LANES_STATE))
 
 
 @pytest.mark.parametrize("precision", ["native", "f32"])
@@ -628,26 +468,14 @@ def test_cooperating_lanes_other_interval_counts(nint, lanes, precision):
     take two moving fronts at a time, odd group sizes leave the upper half one lane more, and with six layers a half of 6 or 8
     lanes is too small for the riders of a deep front: the one-front path takes over).  precision "f32": the same for the
     mixed-precision trapezoid, whose four-node groups (1 .. 31 of them, plus the leftover nodes) are split over the lanes."""
-    import lgar_py_amd as lg
     for name in ("synth1_phil", "six_layer_synth1"):
-        g = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+        g = dict(load(name))
         g["nint"] = np.int64(nint)
 
-        class G(dict):
+        class G_(dict):
             files = list(g)
-        gg = G(g)
-        res = {}
-        for k in (1, lanes):
-            eng = _engine(gg, 3, torch.float64, forward_lanes=k, geff_precision=precision)
-            pr, pe = _forcing(gg, 3)
-            out = eng.forward(pr, pe, series=lg.ACC_NAMES, check=False)
-            res[k] = (out, eng)
-        a, ea = res[1]
-        b, eb = res[lanes]
-        for nm in lg.ACC_NAMES:
-            assert torch.equal(a[nm], b[nm]), (name, nm)
-        for t in ("depth", "theta", "psi", "k", "dzdt", "flags", "n_fronts", "status", "totals"):
-            assert torch.equal(getattr(ea, t), getattr(eb, t)), (name, t)
+        a, b = G.run_lanes_pair(_engine, G_(g), 3, lanes, [f for f in LANES_STATE if f != "scalars"], geff_precision=precision)
+        G.check_bit_identical(a, b, label=name + ": ")
 
 
 @pytest.mark.parametrize("lanes", [4, 6, 21, 64])
@@ -657,21 +485,7 @@ def test_cooperating_lanes_with_the_mixed_precision_trapezoid(name, lanes):
     """geff_precision="f32" on a small job: the lanes of a column split the four-node groups of the mixed-precision trapezoid
     (and the front sweep's evaluations) between them -- every per-step output, the final front tables and the run totals are
     those of the mixed-precision mode with one lane per column BIT FOR BIT."""
-    import lgar_py_amd as lg
-    g = np.load(os.path.join(GOLDEN, name + ".npz"))
-    ncol = 5
-    res = {}
-    for k in (1, lanes):
-        eng = _engine(g, ncol, torch.float64, forward_lanes=k, geff_precision="f32")
-        pr, pe = _forcing(g, ncol)
-        out = eng.forward(pr, pe, series=lg.ACC_NAMES, check=False)
-        res[k] = (out, eng)
-    a, ea = res[1]
-    b, eb = res[lanes]
-    for nm in lg.ACC_NAMES:
-        assert torch.equal(a[nm], b[nm]), nm
-    for t in ("depth", "theta", "psi", "k", "dzdt", "flags", "n_fronts", "status", "scalars", "totals"):
-        assert torch.equal(getattr(ea, t), getattr(eb, t)), t
+    G.check_bit_identical(*G.run_lanes_pair(_engine, load(name), 5, lanes, LANES_STATE, geff_precision="f32"))
 
 
 def test_cooperating_lanes_on_distinct_columns_and_the_default_choice():

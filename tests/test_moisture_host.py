@@ -5,37 +5,15 @@ stand-alone program (tests/moisture_host) and run over the front table the refer
 trajectory fixture.  Its results must equal the numpy statement of the definition (moisture_host.profile_ref) bit for bit, and
 the definition itself must close the reference's mass balance: the storage bins that cover the column sum to the recorded
 ending_volume (Layer.mass_balance, layers/Layer.py:795-824)."""
-import os
-
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, golden_names
+from conftest import golden_names
 
 import moisture_host as MH
 
 TRAJ = [n for n in golden_names() if not n.startswith("grad_")]
 NONMONOTONE = {"manyfronts_pulse_84": (2, 4, 6), "bushland_hourly_1500": (1405,)}  # steps with a front above its predecessor
-
-
-def tables(name, dtype=np.float64):
-    """The reference's front table at every recorded step before its crash, one step per column: arrays laid out like
-    LgarEngine.fronts() plus thickness [L, T], the total thickness Z and the recorded ending_volume [T]."""
-    g = np.load(os.path.join(GOLDEN, name + ".npz"))
-    crash = int(g["crash_step"])
-    T = crash if crash >= 0 else g["forcing"].shape[0]
-    lay = g["front_layer"][:T].T
-    t = dict(depth=np.ascontiguousarray(g["fronts"][:T, :, 0].T.astype(dtype)),
-             theta=np.ascontiguousarray(g["fronts"][:T, :, 1].T.astype(dtype)),
-             layer=lay, flags=np.where(lay >= 0, lay, 0).astype(np.uint8), n_fronts=g["nfronts"][:T].astype(np.int32),
-             thickness=np.repeat(g["thickness"].astype(dtype)[:, None], T, axis=1))
-    F = min(t["depth"].shape[0], 32)  # (manyfronts_pulse_84 records 40 slots, 31 in use)
-    assert int(t["n_fronts"].max()) <= F
-    for k in ("depth", "theta", "layer", "flags"):
-        t[k] = np.ascontiguousarray(t[k][:F])
-    t["Z"] = float(np.cumsum(g["thickness"].astype(np.float64))[-1])
-    t["volume"] = g["acc"][:T, 9]
-    return t
 
 
 def explicit_edges(Z):
@@ -51,7 +29,7 @@ def results():
     cases, keys = [], []
     for name in TRAJ:
         for dtype in (np.float64, np.float32):
-            t = tables(name, dtype)
+            t = MH.tables(name, dtype)
             for edges in (explicit_edges(t["Z"]), None):
                 for what in ("theta", "storage"):
                     cases.append(dict(t, edges=edges, what=what))
@@ -102,7 +80,7 @@ def test_mass_closure_on_the_reference_alone(results):
 
 def test_bins_below_the_column():
     """A bin wholly below the column: theta NaN, storage 0.  A bin straddling the bottom is divided by its in-column width."""
-    t = tables("synth1_phil")
+    t = MH.tables("synth1_phil")
     Z = t["Z"]  # 200 cm
     edges = [0.0, 44.0, Z - 10.0, Z + 10.0, Z + 20.0, Z + 30.0]
     th, st = MH.run_cases([dict(t, edges=edges, what="theta"), dict(t, edges=edges, what="storage")])
@@ -118,7 +96,7 @@ def test_bins_below_the_column():
 
 def test_more_bins_than_the_smallest_kernel_capacity():
     """9, 16, 17 and LGAR_MOIST_BINS bins take the 16- and 32-bin instances of the function."""
-    t = tables("six_layer_synth1")
+    t = MH.tables("six_layer_synth1")
     for nb in (9, 16, 17, 32):
         edges = np.linspace(0.0, t["Z"] + 7.0, nb + 1)
         for what in ("theta", "storage"):
@@ -132,7 +110,7 @@ def test_sanitizer_build_on_fixtures_and_a_corrupt_state():
     meaning, the counts are clamped and nothing is read out of bounds.  Any finding aborts the program."""
     cases = []
     for name in ("manyfronts_pulse_84", "six_layer_synth1"):
-        t = tables(name)
+        t = MH.tables(name)
         cases += [dict(t, edges=explicit_edges(t["Z"]), what="theta"), dict(t, edges=None, what="storage")]
     N, F, L = 5, 8, 3
     rng = np.random.default_rng(0)

@@ -3,7 +3,7 @@ import os, sys, time, json, tempfile
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-from test_host_io import write_forcing, write_soil_dat
+from _model_files import write_forcing, write_soil_dat
 from lgar_py_amd import config
 from lgar_py_amd.data import Data
 from lgar_py_amd.model import MassBalance, dpLGAR
