@@ -240,6 +240,47 @@ int32_t lgar_soil_moisture(const LgarDims *dims, const LgarParams *params, const
                            int32_t n_bins, int32_t what, void *out, const void *weights, double *basin, int32_t dtype,
                            void *stream);
 
+/* Catchment sums: per-row sums of a stored series over MANY catchments, out[t][b] for B catchments at once (LgarStepOut.basin
+ * is the one-catchment case; what a NextGen-style job compares with observations is the [T][B] matrix of catchment runoff).
+ *
+ * Catchment map (CSR).  offsets: int32[n_catchments + 1], non-decreasing, offsets[0] = 0.  order: int32[n_order] column
+ * indices, n_order = offsets[n_catchments], or NULL: the members of catchment b are then the contiguous columns
+ * offsets[b] .. offsets[b + 1] - 1.  A column belongs to at most one catchment and may belong to none.
+ *
+ * For row t and catchment b with n members c_0 .. c_{n-1} in map order:
+ *   - the term is x_i = (double)w[c_i] * (double)series[t][c_i]; w = 1 when weights == NULL (the product is exact for fp32);
+ *   - member i is SKIPPED ENTIRELY (no term, not 0 * NaN) when status != NULL and status[c_i] & LGAR_ST_FAULT_MASK is
+ *     non-zero, and also when c_i is outside [0, n_columns);
+ *   - there are 256 partials s_p, p = i mod 256, each accumulated from +0.0 in increasing i with plain fp64 adds (the library
+ *     is built with -ffp-contract=off);
+ *   - q_l = (s_l + s_{l+64}) + (s_{l+128} + s_{l+192}) for l = 0 .. 63;
+ *   - then for off = 32, 16, 8, 4, 2, 1: q_l <- q_l + q_{l xor off} (every l at once);
+ *   - out[t][b] = q_0; an empty catchment gives +0.0.
+ * out[t][b] is WRITTEN, not added: exactly one wavefront owns it (lane l holds the partials l, l + 64, l + 128, l + 192), there
+ * are no atomics and the caller zeroes nothing.  The result for catchment b is therefore a pure function of its own members'
+ * values, weights and order: it does not depend on n_catchments, on the other catchments, on where the members sit in the
+ * launch, or on the run.
+ *
+ * series: [n_rows][n_columns] (dtype), e.g. a stored LgarStepOut.series[j] or lgar_soil_moisture's [n_bins][n_columns].
+ * weights: [n_columns] (dtype) or NULL.  status: int32[n_columns] or NULL.  out: fp64 [n_rows][n_catchments].
+ * weight_sums: NULL, or fp64[n_catchments]: the same sum, in the same order and with the same skipping, over the terms
+ *   (double)w[c_i] -- what turns a sum into a mean over the columns that are still valid.
+ * Memory safety before meaning: offsets[b] and offsets[b + 1] are clamped into [0, len] (len = n_order, or n_columns without
+ * `order`) before use and a catchment whose clamped end is not beyond its start is empty, so a corrupt map cannot index out of
+ * bounds (its sums are not meaningful).  n_rows = 0 with weight_sums computes the weight sums alone. */
+int32_t lgar_catchment_sums(const void *series, int32_t n_rows, int32_t n_columns, const int32_t *offsets, int32_t n_catchments,
+                            const int32_t *order, int32_t n_order, const void *weights, const int32_t *status, double *out,
+                            double *weight_sums, int32_t dtype, void *stream);
+
+/* Spread, the adjoint of the catchment sums: from a [n_rows][n_catchments] fp64 gradient of the sums to the [n_rows][n_columns]
+ * tangent weights lgar_forward_tangent takes (w_runoff / w_perc):
+ *     out[t][c] = round_to_dtype(grad[t][catchment_of[c]] * (double)w[c])
+ * and 0 where catchment_of[c] is outside [0, n_catchments) (-1: the column belongs to no catchment) or status[c] has a bit of
+ * LGAR_ST_FAULT_MASK.  catchment_of: int32[n_columns]; weights ([n_columns], dtype) and status may be NULL. */
+int32_t lgar_catchment_spread(const double *grad, int32_t n_rows, int32_t n_catchments, const int32_t *catchment_of,
+                              int32_t n_columns, const void *weights, const int32_t *status, void *out, int32_t dtype,
+                              void *stream);
+
 /* Run totals of a run cut into several lgar_forward calls.  lgar_forward sums a call's accumulators step by step from zero
  * and adds that sum to LgarState.totals, so a chunked run adds several partial sums where one call adds one: the same numbers in
  * another order, equal to the last bits only.  This replays the one-call order over series the chunks stored: for every j < 7

@@ -25,7 +25,7 @@ STATUS_NAMES = {1: "NaN", 2: "negative pow base", 4: "theta order", 8: "front ov
                 32: "front reached domain bottom", 64: "structural error"}
 ABI_VERSION = 3  # LGAR_ABI_VERSION of include/lgar.h this binding mirrors
 EXPORTS = ["lgar_version", "lgar_abi_version", "lgar_sizeof_dims", "lgar_fmax", "lgar_lmax", "lgar_cooperating_lanes", "lgar_state_init", "lgar_forward", "lgar_forward_tangent",
-           "lgar_soil_moisture", "lgar_totals_replay", "lgar_leaf_batch", "lgar_valu_probe", "lgar_valu_probe_insts"]
+           "lgar_soil_moisture", "lgar_totals_replay", "lgar_catchment_sums", "lgar_catchment_spread", "lgar_leaf_batch", "lgar_valu_probe", "lgar_valu_probe_insts"]
 
 
 class LgarDims(C.Structure):
@@ -129,6 +129,11 @@ def load():
         lib.lgar_soil_moisture.argtypes = [p(LgarDims), p(LgarParams), p(LgarState), vp, i32, i32, vp, vp, vp, i32, vp]
         lib.lgar_totals_replay.restype = i32
         lib.lgar_totals_replay.argtypes = [p(LgarDims), p(LgarStepOut), i32, vp, i32, vp]
+    if hasattr(lib, "lgar_catchment_sums") or not os.environ.get("LGAR_LIB"):  # (a library selected by hand may predate them)
+        lib.lgar_catchment_sums.restype = i32
+        lib.lgar_catchment_sums.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp]
+        lib.lgar_catchment_spread.restype = i32
+        lib.lgar_catchment_spread.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, i32, vp]
     lib.lgar_leaf_batch.restype = i32
     lib.lgar_leaf_batch.argtypes = [i32, i32, vp, vp, dbl, vp, vp, vp, vp, vp, i32, dbl, vp, i32, vp]
     lib.lgar_valu_probe_insts.restype = i32

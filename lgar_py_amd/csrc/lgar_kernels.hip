@@ -5,6 +5,7 @@
 
 #include <type_traits>
 
+#include "lgar_catchment.hpp"
 #include "lgar_geff.hpp"
 #include "lgar_host.hpp"
 #include "lgar_launch.hpp"
@@ -263,6 +264,25 @@ int32_t lgar_totals_replay(const LgarDims *dims, const LgarStepOut *stored, int3
   if (!stored || !running || n_rows < 0 || (dtype != LGAR_F32 && dtype != LGAR_F64)) return LGAR_E_ARG;
   if (n_rows == 0) return 0;
   return launch_totals_replay(dims, stored, n_rows, running, dtype, (hipStream_t)stream);
+}
+
+int32_t lgar_catchment_sums(const void *series, int32_t n_rows, int32_t n_columns, const int32_t *offsets, int32_t n_catchments,
+                            const int32_t *order, int32_t n_order, const void *weights, const int32_t *status, double *out,
+                            double *weight_sums, int32_t dtype, void *stream) {
+  if (n_rows < 0 || n_columns < 0 || n_catchments < 0 || !offsets || (order && n_order < 0)) return LGAR_E_ARG;
+  // (a job without columns has nothing to read: every sum is +0.0, and an empty series may come as a null pointer)
+  if (n_rows > 0 && n_catchments > 0 && (!out || (!series && n_columns > 0))) return LGAR_E_ARG;
+  return launch_catchment_sums(series, n_rows, n_columns, offsets, n_catchments, order, n_order, weights, status, out, weight_sums,
+                               dtype, (hipStream_t)stream);
+}
+
+int32_t lgar_catchment_spread(const double *grad, int32_t n_rows, int32_t n_catchments, const int32_t *catchment_of,
+                              int32_t n_columns, const void *weights, const int32_t *status, void *out, int32_t dtype,
+                              void *stream) {
+  if (n_rows < 0 || n_columns < 0 || n_catchments < 0) return LGAR_E_ARG;
+  if (n_rows > 0 && n_columns > 0 && (!catchment_of || !out || (n_catchments > 0 && !grad))) return LGAR_E_ARG;
+  return launch_catchment_spread(grad, n_rows, n_catchments, catchment_of, n_columns, weights, status, out, dtype,
+                                 (hipStream_t)stream);
 }
 
 int32_t lgar_leaf_batch(int32_t op, int32_t n_items, const void *x, const void *y, double z, const void *alpha,

@@ -215,8 +215,19 @@ class LgarEngine:
         so.counters = self.counters.data_ptr()
         return so
 
+    def _scratch_series(self, nm, T):
+        """The [T, N] scratch series behind a sum over `nm` whose series the caller did not ask for (kept for the next call of
+        the same T), or None when all such buffers together would pass basin_scratch_bytes."""
+        if self._basin_scratch[0] != T:  # buffers of one call shape at a time
+            self._basin_scratch = (T, {})
+        scratch = self._basin_scratch[1].get(nm)
+        one = T * self.N * self.totals.element_size()
+        if scratch is None and (len(self._basin_scratch[1]) + 1) * one <= self.basin_scratch_bytes:
+            scratch = self._basin_scratch[1][nm] = self._new_series(T, self.N, dtype=self.dtype, device=self.device)
+        return scratch
+
     def forward(self, precip, pet, series=("runoff", "percolation"), out=None, check=True, basin=(), weights=None,
-                call_sums=False, forcing_group=1):
+                call_sums=False, forcing_group=1, catchments=None, catchment=()):
         """Advance every column by T forcing steps.  precip/pet: [T, N] cm/h on self.device, or [T, Nf] with Nf dividing N
         (broadcast: column c reads forcing column c % Nf; Nf = 1 is one basin series for every column); with forcing_group
         G > 1, G consecutive columns share a forcing column: column c reads (c // G) % Nf.
@@ -229,7 +240,14 @@ class LgarEngine:
         kept for the next call of the same T -- as long as all such buffers together stay within the engine's
         basin_scratch_bytes (default 8 GiB; 0 = never); past that the sum falls back to the in-kernel atomics and nothing is
         allocated.  release_scratch() frees them.  call_sums=True adds "call_sums": [NACC, N], the accumulators summed over this
-        call's steps (rows 8, 9: latest ponded_water / ending_volume)."""
+        call's steps (rows 8, 9: latest ponded_water / ending_volume).
+        catchments: a catchments.CatchmentMap over this engine's columns, catchment: names whose per-step sums over EACH
+        catchment are wanted: returned under "catchment:<name>" as fp64 [T, B], with "catchment:weight" [B], the sums of the
+        weights (the map's own; `weights` above belongs to the basin sums) of the columns that have not faulted.  They are
+        taken from the stored series after the launch (lgar_catchment_sums, include/lgar.h: a fixed summation order per
+        catchment, the same bits on every run) with the engine's status, so a faulted column drops out of every row.  A name
+        that is not in `series` gets a scratch series by the rule above; past the budget this raises (there is no in-kernel
+        catchment sum)."""
         self._need_state()
         precip, pet = self._forcing(precip, pet, forcing_group)
         T = precip.shape[0]
@@ -248,24 +266,40 @@ class LgarEngine:
                 # LgarStepOut.basin); the in-kernel atomics are ~10x as expensive, so a name whose series the caller does
                 # not want still gets a scratch series (kept for the next call of the same shape) unless it would be huge
                 if nm not in stored:
-                    if self._basin_scratch[0] != T:  # buffers of one call shape at a time
-                        self._basin_scratch = (T, {})
-                    scratch = self._basin_scratch[1].get(nm)
-                    one = T * self.N * self.totals.element_size()
-                    if scratch is None and (len(self._basin_scratch[1]) + 1) * one <= self.basin_scratch_bytes:
-                        scratch = self._basin_scratch[1][nm] = self._new_series(T, self.N, dtype=self.dtype, device=self.device)
+                    scratch = self._scratch_series(nm, T)
                     if scratch is not None:
                         stored[nm] = scratch
             if weights is not None:
                 w = torch.as_tensor(weights).to(self.device, self.dtype).contiguous()
                 if tuple(w.shape) != (self.N,):
                     raise LgarError("weights must be [N]")
+        if catchments is not None:
+            if getattr(catchments, "N", None) != self.N or catchments.ids.device != self.status.device:
+                raise LgarError("catchments must be a CatchmentMap over this engine's %d columns on %s" % (self.N, self.device))
+            for nm in catchment:
+                if nm not in ACC_NAMES:
+                    raise LgarError("unknown catchment sum %r (one of %s)" % (nm, ", ".join(ACC_NAMES)))
+                if nm not in stored:
+                    stored[nm] = self._scratch_series(nm, T)
+                    if stored[nm] is None:
+                        raise LgarError("the catchment sum of %r needs a [%d, %d] series and basin_scratch_bytes = %d does not "
+                                        "allow it: ask for the series (series=...) or raise the budget"
+                                        % (nm, T, self.N, self.basin_scratch_bytes))
+        elif catchment:
+            raise LgarError("catchment=%r needs catchments=<CatchmentMap>" % (tuple(catchment),))
         if call_sums:
             res["call_sums"] = torch.zeros(NACC, self.N, dtype=self.dtype, device=self.device)
         so = self._step_out(stored, block, basin, w, res.get("call_sums"))
         fo = _capi.LgarForcing(precip.data_ptr(), pet.data_ptr())
         self._call("forward", C.byref(self.dims), C.byref(self._params), C.byref(self._state), C.byref(fo), C.byref(so),
                    self.status.data_ptr())
+        if catchments is not None:
+            # from the stored series, after the launch on the same stream, with the status the launch left: a column that
+            # faulted drops out of every row (the rows after its fault were never written)
+            for nm in catchment:
+                res["catchment:" + nm] = catchments.sums(stored[nm], status=self.status)
+            no_rows = torch.empty(0, self.N, dtype=self.dtype, device=self.device)
+            res["catchment:weight"] = catchments.sums(no_rows, status=self.status, weight_sums=True)[1]
         if check:
             self.check_status()
         return res

@@ -261,10 +261,14 @@ class dpLGAR(nn.Module):
                      dzdt=float(fr["dzdt"][i, column]), layer_num=int(fr["layer"][i, column]),
                      to_bottom=bool(fr["to_bottom"][i, column])) for i in range(nf)]
 
-    def soil_moisture(self, edges=None, what="theta"):
+    def soil_moisture(self, edges=None, what="theta", catchments=None):
         """Depth-binned water content as the front table stands now (LgarEngine.soil_moisture; the slot the reference
         reserves as GlobalParams.soil_moisture_wetting_fronts, physics/GlobalParams.py:61): edges [D + 1] in cm -> [D, N],
-        None = the soil layers -> [L, N]; one column gives [D] / [L], like ending_volume.  fp64 on the accumulators' device."""
+        None = the soil layers -> [L, N]; one column gives [D] / [L], like ending_volume.  fp64 on the accumulators' device.
+        catchments: a catchments.CatchmentMap over the columns -> fp64 [D, B] on the engine's device instead: the (weighted)
+        STORAGE of every bin summed per catchment over the columns that have not faulted (`what` is not consulted)."""
+        if catchments is not None:
+            return catchments.sums(self.engine.soil_moisture(edges, "storage"), status=self.engine.status)
         sm = self.engine.soil_moisture(edges, what).to(self.attr_device, torch.float64)
         return sm[:, 0] if self.n_columns == 1 else sm
 
