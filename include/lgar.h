@@ -145,9 +145,28 @@ typedef struct {
                                             one workgroup per block. */
 } LgarState;
 
-/* Forcing, each [n_steps][forcing_columns], cm/h (data/Data.py:32-37). */
+/* Forcing, each [n_steps][forcing_columns], cm/h (data/Data.py:32-37).
+ *
+ * column_map: NULL (the layouts of LgarDims.forcing_columns / forcing_group above, bit for bit), or a per-column forcing
+ * index in device memory -- B catchments of unequal size, each with its own series, without a gathered [n_steps][n_columns]
+ * copy.  With column_map != NULL:
+ *  - G = forcing_group (>= 1, n_columns % G == 0 as ever); the map is int32[M], M = n_columns / G.
+ *  - Nf = LgarDims.forcing_columns is the number of forcing columns: it must be >= 1 (else LGAR_E_ARG) and needs NO
+ *    divisibility relation to n_columns; precip / pet are [n_steps][Nf].
+ *  - soil column c reads forcing column m(c) = min(max(column_map[c / G], 0), Nf - 1) at every step.  The clamp is memory
+ *    safety before meaning, as in lgar_catchment_sums: the library never reads device memory on the host, so a corrupt map
+ *    cannot index out of bounds (what such a column computes is not meaningful).  The index is read ONCE per column, before
+ *    the time loop.
+ *  - lgar_forward_tangent reads precip / pet the same way; its weights w_runoff / w_perc are then [n_steps][M] and column c
+ *    reads weight column c / G.  (Weights cannot go through the map: the gradient of a catchment sum with respect to a member
+ *    column carries that column's own area weight, so it is [n_steps][n_columns] by nature -- lgar_catchment_spread produces
+ *    exactly that.  Without a map the weights keep the forcing's [n_steps][Nf] layout.)  tangent_share = W: the caller's
+ *    guarantee is unchanged; with a map it holds whenever G % W == 0, since all columns of a group index one map entry.
+ *  - the result for column c is, bit for bit, that of an unmapped call with precip'[t][c] = precip[t][m(c)], pet' likewise,
+ *    in every kernel family (fp32, fp64, mixed, cooperating lanes, literal, every capacity of the chain, the tangent). */
 typedef struct {
   const void *precip, *pet;
+  const int32_t *column_map;
 } LgarForcing;
 
 /* Optional per-step outputs.
@@ -179,9 +198,10 @@ typedef struct {
 
 const char *lgar_version(void);
 /* ABI revision of this header: bumped whenever a struct of this file changes size or layout or an entry point changes its
- * argument list (3: LgarDims.geff_mode / forward_lanes, lgar_forward_tangent's `tickets`).  A caller compares it with the
+ * argument list (3: LgarDims.geff_mode / forward_lanes, lgar_forward_tangent's `tickets`; 4: LgarForcing.column_map -- a caller
+ * built against 3 would pass a two-pointer LgarForcing and the library would read past it).  A caller compares it with the
  * LGAR_ABI_VERSION it was compiled against, and lgar_sizeof_dims() with its own sizeof(LgarDims), before the first call. */
-#define LGAR_ABI_VERSION 3
+#define LGAR_ABI_VERSION 4
 int32_t lgar_abi_version(void);
 int32_t lgar_sizeof_dims(void);
 int32_t lgar_fmax(void);

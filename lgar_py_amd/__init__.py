@@ -5,5 +5,7 @@
 from ._capi import ACC_NAMES, FMAX, LMAX, LgarError  # noqa: F401
 from .catchments import CatchmentMap, catchment_sum  # noqa: F401
 from .engine import LgarEngine, LgarStatusError, leaf_batch  # noqa: F401
+from .forcing import ForcingMap  # noqa: F401
 
-__all__ = ["LgarEngine", "LgarError", "LgarStatusError", "leaf_batch", "CatchmentMap", "catchment_sum", "ACC_NAMES", "FMAX", "LMAX"]
+__all__ = ["LgarEngine", "LgarError", "LgarStatusError", "leaf_batch", "CatchmentMap", "catchment_sum", "ForcingMap", "ACC_NAMES", "FMAX",
+           "LMAX"]

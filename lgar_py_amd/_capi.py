@@ -23,7 +23,7 @@ ACC_NAMES = ["precip", "PET", "AET", "infiltration", "runoff", "percolation", "g
 ST_NAN, ST_NEGBASE, ST_THETA_ORDER, ST_OVERFLOW, ST_ITERCAP, ST_BOTTOM, ST_STRUCT = 1, 2, 4, 8, 16, 32, 64
 STATUS_NAMES = {1: "NaN", 2: "negative pow base", 4: "theta order", 8: "front overflow", 16: "iteration cap",
                 32: "front reached domain bottom", 64: "structural error"}
-ABI_VERSION = 3  # LGAR_ABI_VERSION of include/lgar.h this binding mirrors
+ABI_VERSION = 4  # LGAR_ABI_VERSION of include/lgar.h this binding mirrors
 EXPORTS = ["lgar_version", "lgar_abi_version", "lgar_sizeof_dims", "lgar_fmax", "lgar_lmax", "lgar_cooperating_lanes", "lgar_state_init", "lgar_forward", "lgar_forward_tangent",
            "lgar_soil_moisture", "lgar_totals_replay", "lgar_catchment_sums", "lgar_catchment_spread", "lgar_leaf_batch", "lgar_valu_probe", "lgar_valu_probe_insts"]
 
@@ -48,7 +48,8 @@ class LgarState(C.Structure):
 
 
 class LgarForcing(C.Structure):
-    _fields_ = [("precip", C.c_void_p), ("pet", C.c_void_p)]
+    # (LgarForcing(precip, pet) leaves column_map NULL: no map)
+    _fields_ = [("precip", C.c_void_p), ("pet", C.c_void_p), ("column_map", C.c_void_p)]
 
 
 class LgarStepOut(C.Structure):

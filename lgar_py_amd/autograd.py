@@ -26,13 +26,14 @@ BATCH_DIRECTIONS_MAX_COLUMNS = 1 << 23
 SHARE_MIN_LANES = 65536  # columns x directions: one wave on every SIMD of the chip
 
 
-def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True):
+def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcing_map=None):
     """Vector-Jacobian product for every (kind, layer) in `wanted` (list of (kind, l)).
     Returns ({(kind, l): grad[N]}, tangent_status[N]).  Columns are independent, so the directions are laid side by side as
     len(wanted) * N columns of a single launch (fills the chip even for ensembles of 10^5 columns; very large jobs go in
     groups of directions).  A column whose tangent integration faults (status != 0: NaN, iteration cap, front overflow
     ...) has no valid gradient: with check=True that raises LgarStatusError (a ValueError, like the reference's physics
-    faults), with check=False its gradient entries are zeroed and the status tensor says which columns those are."""
+    faults), with check=False its gradient entries are zeroed and the status tensor says which columns those are.
+    forcing_map: a forcing.ForcingMap with one entry per column -- precip / pet are [T, B], the weights stay [T, N]."""
     L, N, D = eng.L, eng.N, len(wanted)
     out = {}
     status = torch.zeros(N, dtype=torch.int32, device=eng.device)
@@ -53,7 +54,7 @@ def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True):
             kind, l = part[0]
             dmat = torch.zeros(L, N, dtype=eng.dtype, device=eng.device)
             dmat[l] = 1.0
-            out[(kind, l)], _, st = eng.tangent({kind: dmat}, precip, pet, w_runoff=w_runoff, w_perc=w_perc)
+            out[(kind, l)], _, st = eng.tangent({kind: dmat}, precip, pet, w_runoff=w_runoff, w_perc=w_perc, forcing_map=forcing_map)
             status |= st
             continue
         # column n's Dg directions sit in ADJACENT lanes (column n * Dg + b): they follow the same branches, so a wavefront
@@ -65,7 +66,10 @@ def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True):
         for b, (kind, l) in enumerate(part):
             dirs[kind][l, b::Dg] = 1.0
         g, _, st = big.tangent(dirs, precip, pet, w_runoff=w_runoff, w_perc=w_perc, forcing_group=Dg,  # forcing / weights broadcast by the kernel
-                               share=Dg if share else 0)
+                               share=Dg if share else 0,
+                               # the SAME map, not replicated: entry c // Dg of the launch is the original column, and the
+                               # incoming [T, N] gradient is the [T, Dg * N // Dg] weight array as it is
+                               forcing_map=forcing_map)
         for b, key in enumerate(part):
             out[key] = g[b::Dg].contiguous()
             status |= st[b::Dg]
@@ -89,9 +93,12 @@ class LgarSeriesFunction(torch.autograd.Function):
         engine_kw = dict(engine_kw)
         check = engine_kw.pop("check", True)
         status_out = engine_kw.pop("status_out", None)
+        fmap = engine_kw.pop("forcing_map", None)
         eng = LgarEngine(alpha.detach(), n.detach(), ksat.detach(), theta_e, theta_r, thickness, **engine_kw)
         precip, pet = torch.as_tensor(precip), torch.as_tensor(pet)
-        if precip.dim() == 2 and precip.shape[1] != eng.N:
+        if fmap is not None:
+            pass  # [T, B] forcing through the map, forward and backward: nothing is expanded (the weights do not go through it)
+        elif precip.dim() == 2 and precip.shape[1] != eng.N:
             # broadcast forcing [T, Nf]: the backward pass pairs the forcing with the incoming [T, N] gradient column by
             # column (the tangent kernels take one layout for both), so the series is expanded here, once
             if eng.N % max(int(precip.shape[1]), 1) != 0 or precip.shape != pet.shape:
@@ -99,11 +106,12 @@ class LgarSeriesFunction(torch.autograd.Function):
                                 % (eng.N, tuple(precip.shape), tuple(pet.shape)))
             rep = eng.N // int(precip.shape[1])
             precip, pet = precip.repeat(1, rep).contiguous(), pet.repeat(1, rep).contiguous()  # column c reads c % Nf
-        out = eng.forward(precip, pet, series=("runoff", "percolation"), check=check)
+        out = eng.forward(precip, pet, series=("runoff", "percolation"), check=check, forcing_map=fmap)
         if status_out is not None:
             status_out.append(eng.status)
         ctx.engine = eng
         ctx.forcing = (precip, pet)
+        ctx.forcing_map = fmap
         ctx.in_dtypes = (alpha.dtype, n.dtype, ksat.dtype)
         ctx.check = check
         ctx.status_out = status_out
@@ -119,7 +127,7 @@ class LgarSeriesFunction(torch.autograd.Function):
         keep = (~fwd_bad).to(g_runoff.dtype)[None, :] if g_runoff is not None else None
         gr = None if g_runoff is None else g_runoff * keep
         gp = None if g_perc is None else g_perc * ((~fwd_bad).to(g_perc.dtype)[None, :])
-        vj, st = parameter_vjp(eng, precip, pet, gr, gp, wanted, check=False)
+        vj, st = parameter_vjp(eng, precip, pet, gr, gp, wanted, check=False, forcing_map=ctx.forcing_map)
         st = torch.where(fwd_bad, torch.zeros_like(st), st)
         if ctx.status_out is not None:
             ctx.status_out.append(st)  # [forward status, tangent status]
@@ -140,7 +148,8 @@ def lgar_series(alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, **engi
     """Differentiable run: parameters [L, N] (torch tensors, may require grad), forcing [T, N] -> runoff, percolation [T, N].
     engine_kw: LgarEngine keywords, plus check=False to keep going when columns fault: pass status_out=[] to receive the
     forward status tensor (appended by the forward pass) and the tangent status tensor (appended by the backward pass);
-    faulted columns get zero gradient."""
+    faulted columns get zero gradient.  forcing_map=<forcing.ForcingMap>: the forcing is [T, B] and column c reads forcing column
+    forcing_map.index[c], in the forward run and in the backward pass alike: no [T, N] forcing exists anywhere."""
     return LgarSeriesFunction.apply(alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, engine_kw)
 
 

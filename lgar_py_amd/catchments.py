@@ -13,6 +13,7 @@ import torch
 
 from . import _capi
 from ._capi import LgarError
+from .forcing import ForcingMap
 
 
 def _dtype_code(dtype):
@@ -84,6 +85,17 @@ class CatchmentMap:
         if dtype not in self._weights:
             self._weights[dtype] = self.weights_host.to(self.device, dtype).contiguous()
         return self._weights[dtype]
+
+    def forcing_map(self):
+        """The forcing.ForcingMap of the ids (made once): every column reads the forcing column of its own catchment, so [T, B]
+        forcing goes into LgarEngine.forward / autograd.lgar_series as it is.  A column of no catchment (id -1) has no forcing
+        and cannot run: that raises."""
+        if getattr(self, "_forcing_map", None) is None:
+            if self.N and int(self.ids_host.min()) < 0:
+                raise LgarError("%d columns belong to no catchment (id -1): a column without forcing cannot run"
+                                % int((self.ids_host < 0).sum()))
+            self._forcing_map = ForcingMap(self.ids_host, n_forcing=self.B, device=self.device)
+        return self._forcing_map
 
     # ------------------------------------------------------------------------------------------
     def _lib(self):

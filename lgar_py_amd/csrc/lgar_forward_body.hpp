@@ -38,6 +38,9 @@ template <typename R> struct KArgs {
   unsigned long long *counters;                           // [LGAR_NCOUNTERS] or null (measurement: Geff wave-calls ...)
   R *call_sums;                                           // [NACC][N] or null: accumulators summed over this call's steps
   Glob<R> G;
+  const int32_t *fmap;                                    // null, or [N / Fg] (LgarForcing.column_map): column c reads forcing
+                                                          // column clamp(fmap[c / Fg], 0, Nf - 1).  Last, so that every other
+                                                          // member keeps its place in the argument block
 };
 
 // Per-call sums of the accumulators that fit in the wave's LDS budget next to the front table.  They are touched once per
@@ -201,7 +204,10 @@ __device__ __forceinline__ void init_lane(const LGAR_KARG KArgs<R> *ap, size_t c
 // Cooperating lanes (a.coop = 4..64, jobs too small to fill the chip): that many adjacent lanes integrate the SAME column c
 // redundantly -- same loads, same values, same branches -- and split the nodes of the Geff trapezoid between them (xchg: the
 // wave's exchange buffer); `leader` is true for the one lane of the group that stores the column's results.
-template <typename R, int NL, int FMAX, int MODE>
+// MAPPED: whether the forcing column comes from LgarForcing.column_map -- 1 / 0: decided where the kernel is compiled (the
+// library has every forward kernel twice, and the one without a map is instruction for instruction what it was before the map
+// existed: these kernels' register allocation does not forgive a branch); -1: looked up in the argument block (the simulator).
+template <typename R, int NL, int FMAX, int MODE, int MAPPED = -1>
 __device__ __forceinline__ void forward_lane(const LGAR_KARG KArgs<R> *ap, size_t c, bool live, int lane,
                                              ForwardLDS<R, FMAX, MODE> &lds, bool leader = true, R *xchg = nullptr, int group = 0,
                                              int rank = 0) {
@@ -316,7 +322,15 @@ __device__ __forceinline__ void forward_lane(const LGAR_KARG KArgs<R> *ap, size_
     if (a.series[j]) series_mask |= 1u << j;
   const int T = a.T;
   const size_t Nf = (size_t)a.Nf;
-  const size_t cf = (Nf == N) ? c : (c / (size_t)a.Fg) % Nf;  // this column's forcing column
+  // this column's forcing column: by the layout, or -- LgarForcing.column_map -- by the caller's index, read HERE, once, and
+  // clamped (a corrupt map cannot index out of bounds).  Either way it is the one value `cf` the time loop carries.
+  size_t cf;
+  if (MAPPED < 0 ? (a.fmap != nullptr) : (MAPPED != 0)) {
+    const int m = a.fmap[c / (size_t)a.Fg];
+    cf = (size_t)(m < 0 ? 0 : (m < a.Nf ? m : a.Nf - 1));
+  } else {
+    cf = (Nf == N) ? c : (c / (size_t)a.Fg) % Nf;
+  }
   // (MODE_COOP, one wave per SIMD and registers to spare: the NEXT step's forcing is loaded a step ahead -- a lone wave has nothing
   // else to cover the ~1 us of that load with)
   constexpr bool AHEAD = M::coop;

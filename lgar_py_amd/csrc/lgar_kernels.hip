@@ -194,6 +194,8 @@ int32_t lgar_forward(const LgarDims *dims, const LgarParams *params, LgarState *
   if (rc) return rc;
   rc = check_state(params, state, status);
   if (rc) return rc;
+  rc = check_forcing_layout(dims, forcing);
+  if (rc) return rc;
   if (dims->n_steps == 0) return 0;  // empty run: nothing to read
   if (!forcing || !forcing->precip || !forcing->pet) return LGAR_E_ARG;
   // basin sums of accumulators whose series this call stores anyway are taken from the stored series afterwards (one pass,
@@ -232,6 +234,8 @@ int32_t lgar_forward_tangent(const LgarDims *dims, const LgarParams *params, con
   if (!params->alpha || !params->n || !params->ksat || !params->theta_e || !params->theta_r || !params->thickness)
     return LGAR_E_ARG;
   if (dims->n_steps > 0 && (!forcing->precip || !forcing->pet)) return LGAR_E_ARG;
+  rc = check_forcing_layout(dims, forcing);
+  if (rc) return rc;
   return by_layers(dims->n_layers, [&](auto nl) {
     return launch_tangent_nl<decltype(nl)::value>(dims, params, direction, forcing, w_runoff, w_perc, grad_out, tangent_runoff,
                                                   status, dtype, (hipStream_t)stream, tickets);

@@ -52,50 +52,25 @@ template <typename R, int MODE> struct CoopLDS {
   R tab[on ? LGAR_COOP_GROUPS : 1][on ? LGAR_COOP_TAB_ROW : 1];
 };
 
+// Every forward kernel exists twice: as it always was, and reading its forcing through LgarForcing.column_map.  The index is
+// one load per column before the time loop, but one kernel with both paths ran 1 % slower WITHOUT a map (measured: fp32
+// 11.88 -> 12.00 ms, mixed precision 28.51 -> 28.73 ms, through register allocation alone), so the map is a compile-time
+// matter and the two kernels share their text (lgar_forward_wave.hpp).
 template <typename R, int NL, int CAP, int MODE>
 __global__ __launch_bounds__(WAVE, (Occupancy<R, CAP>::waves)) void lgar_forward_kernel(KArgs<R> a) {
   __shared__ ForwardLDS<R, CAP, MODE> lds;
   __shared__ CoopLDS<R, MODE> coop_lds;
-  const int lane = threadIdx.x;
-  // the argument block is read in place (kernarg segment), see LGAR_KARG in lgar_scalar.hpp
-  const LGAR_KARG KArgs<R> *ap = (const LGAR_KARG KArgs<R> *)__builtin_amdgcn_kernarg_segment_ptr();
-  const size_t N = (size_t)ap->N;
-  unsigned *ticket = ap->ticket;
-  if (ap->pending_in != nullptr && *ap->pending_in == 0u) return;  // no column was handed over to this kernel
-  // With a ticket counter: persistent waves.  The grid is one wave per wave slot of the chip; each pulls 64-column blocks
-  // from the counter until none is left, so no round of the grid is partially filled whatever the column count.
-  // Without: one workgroup per block.
-  // cooperating lanes: `coop` adjacent lanes per column (4..64; 1 = every lane its own column), 64 / coop columns per wave
-  const int coop = CoopLDS<R, MODE>::on ? ap->coop : 1;
-  const unsigned cpb = (unsigned)(WAVE / coop);
-  const unsigned nblocks = (unsigned)((N + cpb - 1) / cpb);
-  for (bool first = true;; first = false) {
-    unsigned blk = blockIdx.x;
-    if (ticket != nullptr) {
-      if (lane == 0) blk = atomicAdd(ticket, 1u);
-      blk = __builtin_amdgcn_readfirstlane(blk);
-      if (blk >= nblocks) break;
-    } else if (!first) {
-      break;
-    }
-    if constexpr (CoopLDS<R, MODE>::on) {
-      if (coop > 1) {
-        // my group and my place in it; the lanes left over when coop does not divide 64 join the last group
-        int group = lane / coop;
-        group = group < (int)cpb ? group : (int)cpb - 1;
-        const int rank = lane - group * coop;
-        const size_t c0 = (size_t)blk * cpb + group;
-        const bool live = c0 < N;
-        // (a wave of at most 8 columns leaves every group two rows of the exchange table: Column::calc_dzdt_pairs)
-        const int rows = (cpb <= LGAR_COOP_GROUPS / 2) ? 2 : 1;
-        forward_lane<R, NL, CAP, MODE>(ap, live ? c0 : N - 1, live, lane, lds, rank == 0, &coop_lds.tab[group * rows][0], group, rank);
-        continue;
-      }
-    }
-    const size_t c0 = (size_t)blk * WAVE + lane;
-    const bool live = c0 < N;
-    forward_lane<R, NL, CAP, MODE>(ap, live ? c0 : N - 1, live, lane, lds);
-  }
+#define LGAR_FORWARD_MAPPED 0
+#include "lgar_forward_wave.hpp"
+#undef LGAR_FORWARD_MAPPED
+}
+template <typename R, int NL, int CAP, int MODE>
+__global__ __launch_bounds__(WAVE, (Occupancy<R, CAP>::waves)) void lgar_forward_mapped_kernel(KArgs<R> a) {
+  __shared__ ForwardLDS<R, CAP, MODE> lds;
+  __shared__ CoopLDS<R, MODE> coop_lds;
+#define LGAR_FORWARD_MAPPED 1
+#include "lgar_forward_wave.hpp"
+#undef LGAR_FORWARD_MAPPED
 }
 
 template <typename R, int NL>
@@ -117,7 +92,8 @@ static void launch_forward_kernel(KArgs<R> &a, unsigned nblocks, unsigned *ticke
     const unsigned slots = wave_slots(Occupancy<R, CAP>::waves);
     grid = nblocks < slots ? nblocks : slots;
   }
-  hipLaunchKernelGGL((lgar_forward_kernel<R, NL, CAP, MODE>), dim3(grid), dim3(WAVE), 0, st, a);
+  if (a.fmap != nullptr) hipLaunchKernelGGL((lgar_forward_mapped_kernel<R, NL, CAP, MODE>), dim3(grid), dim3(WAVE), 0, st, a);
+  else hipLaunchKernelGGL((lgar_forward_kernel<R, NL, CAP, MODE>), dim3(grid), dim3(WAVE), 0, st, a);
 }
 
 // fast-mode kernel of capacity CAP: MODE_FAST, or -- double precision with LgarDims.geff_mode = 1 -- MODE_MIXED (mixed-precision

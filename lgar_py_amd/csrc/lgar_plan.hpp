@@ -57,11 +57,20 @@ inline int check_dims(const LgarDims *d) {
   if (d->search_mode < 0 || d->search_mode > 2) return LGAR_E_ARG;
   if (d->front_slots < 0 || d->front_slots > LGAR_FMAX || (d->front_slots > 0 && d->front_slots < d->n_layers + 1)) return LGAR_E_ARG;
   if (d->forcing_columns < 0 || d->forcing_group < 0 || d->n_columns % forcing_group(d) != 0) return LGAR_E_ARG;
-  if (d->forcing_columns > 0 && (d->n_columns / forcing_group(d)) % d->forcing_columns != 0) return LGAR_E_ARG;
   if (d->tangent_share != 0 && (d->tangent_share < 2 || d->tangent_share > 32 || d->n_columns % d->tangent_share != 0)) return LGAR_E_ARG;
   if (d->geff_mode < 0 || d->geff_mode > 1) return LGAR_E_ARG;
   if (d->forward_lanes < 0 || d->forward_lanes > 64 || d->forward_lanes == 2 || d->forward_lanes == 3) return LGAR_E_ARG;
   if (!(d->dt_h > 0.0)) return LGAR_E_ARG;
+  return 0;
+}
+
+// The forcing layout of a call that READS forcing (lgar_forward, lgar_forward_tangent; check_dims has passed).  It depends on
+// LgarForcing.column_map, so it is not check_dims' business: the entry points that read no forcing (lgar_state_init,
+// lgar_soil_moisture ...) take whatever layout the last call left in the caller's LgarDims.  Without a map the forcing columns
+// divide the groups of columns (broadcast); with one there are simply Nf >= 1 of them.
+inline int check_forcing_layout(const LgarDims *d, const LgarForcing *f) {
+  if (f != nullptr && f->column_map != nullptr) return d->forcing_columns >= 1 ? 0 : LGAR_E_ARG;
+  if (d->forcing_columns > 0 && (d->n_columns / forcing_group(d)) % d->forcing_columns != 0) return LGAR_E_ARG;
   return 0;
 }
 
@@ -90,6 +99,7 @@ inline KArgs<R> make_args(const LgarDims *d, const LgarParams *p, LgarState *s, 
   a.totals = (R *)s->totals;
   a.precip = f ? (const R *)f->precip : nullptr;
   a.pet = f ? (const R *)f->pet : nullptr;
+  a.fmap = f ? f->column_map : nullptr;
   for (int j = 0; j < LGAR_NACC; j++) a.series[j] = o ? (R *)o->series[j] : nullptr;
   a.basin = o ? o->basin : nullptr;
   a.basin_mask = o ? o->basin_mask : 0u;

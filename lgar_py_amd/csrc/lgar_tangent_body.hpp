@@ -26,11 +26,12 @@ template <typename R> struct TArgs {
   const R *alpha, *n, *ksat, *theta_e, *theta_r, *thick;  // [NL][N]
   const R *d_alpha, *d_n, *d_ksat;                        // [NL][N] or null
   const R *precip, *pet;                                  // [T][Nf]
-  const R *w_runoff, *w_perc;                             // [T][Nf] or null
+  const R *w_runoff, *w_perc;                             // [T][Nf] or null; with fmap [T][N / Fg], column c reads c / Fg
   R *grad_out;                                            // [N]
   R *tangent_runoff;                                      // [T][N] or null
   int32_t *status;                                        // [N]
   Glob<R> G;
+  const int32_t *fmap;                                    // null, or [N / Fg] (LgarForcing.column_map), as KArgs::fmap; last
 };
 
 // the argument block of one lgar_forward_tangent call: one kernel on its own, no work counter (as make_args, lgar_plan.hpp)
@@ -53,6 +54,7 @@ inline TArgs<R> make_targs(const LgarDims *d, const LgarParams *p, const LgarPar
   a.d_alpha = (const R *)dir->alpha; a.d_n = (const R *)dir->n; a.d_ksat = (const R *)dir->ksat;
   a.precip = (const R *)f->precip;
   a.pet = (const R *)f->pet;
+  a.fmap = f->column_map;
   a.w_runoff = (const R *)w_runoff;
   a.w_perc = (const R *)w_perc;
   a.grad_out = (R *)grad_out;
@@ -96,7 +98,17 @@ __device__ __forceinline__ void tangent_lane(const LGAR_KARG TArgs<R> *ap, size_
   R grad = R(0);
   bool handed_over = false;
   const size_t Nf = (size_t)a.Nf;
-  const size_t cf = (Nf == N) ? c : (c / (size_t)a.Fg) % Nf;
+  // this column's forcing column: by the layout, or by the caller's index (read here, once, and clamped), as in forward_lane
+  size_t cf;
+  if (a.fmap != nullptr) {
+    const int m = a.fmap[c / (size_t)a.Fg];
+    cf = (size_t)(m < 0 ? 0 : (m < a.Nf ? m : a.Nf - 1));
+  } else {
+    cf = (Nf == N) ? c : (c / (size_t)a.Fg) % Nf;
+  }
+  // The weights: without a map they have the forcing's layout and ONE offset serves both (t * Nf + cf).  With a map they are
+  // [T][N / Fg] and column c reads c / Fg: that offset is worked out where it is used, from values that are at hand anyway
+  // (c, and N and Fg in the argument block), so the loop carries nothing new across a step in either case.
   // One wave per SIMD: nothing else covers a load's latency, so a step's forcing and weights are loaded one step AHEAD (four
   // values in registers across a step; they are taken into their registers before the step's optional store is issued --
   // loads and stores share one counter).
@@ -104,8 +116,9 @@ __device__ __forceinline__ void tangent_lane(const LGAR_KARG TArgs<R> *ap, size_
   if (a.T > 0) {
     precip_ahead = a.precip[cf];
     pet_ahead = a.pet[cf];
-    if (a.w_runoff) wr_ahead = a.w_runoff[cf];
-    if (a.w_perc) wp_ahead = a.w_perc[cf];
+    const size_t ow = (a.fmap != nullptr) ? (size_t)((unsigned)c / (unsigned)a.Fg) : cf;
+    if (a.w_runoff) wr_ahead = a.w_runoff[ow];
+    if (a.w_perc) wp_ahead = a.w_perc[ow];
   }
   for (int t = 0; t < a.T; t++) {
     if (!a.chain_last && col.nf + a.G.nsub > FMAX) {
@@ -114,11 +127,14 @@ __device__ __forceinline__ void tangent_lane(const LGAR_KARG TArgs<R> *ap, size_
     }
     const R precip = precip_ahead, pet = pet_ahead, wr = wr_ahead, wp = wp_ahead;
     {
-      const size_t o = (size_t)((t + 1 < a.T) ? t + 1 : t) * Nf + cf;
+      const size_t tn = (size_t)((t + 1 < a.T) ? t + 1 : t);
+      const size_t o = tn * Nf + cf;
       precip_ahead = a.precip[o];
       pet_ahead = a.pet[o];
-      if (a.w_runoff) wr_ahead = a.w_runoff[o];
-      if (a.w_perc) wp_ahead = a.w_perc[o];
+      size_t ow = o;
+      if (a.fmap != nullptr) ow = tn * (size_t)((unsigned)a.N / (unsigned)a.Fg) + (size_t)((unsigned)c / (unsigned)a.Fg);
+      if (a.w_runoff) wr_ahead = a.w_runoff[ow];
+      if (a.w_perc) wp_ahead = a.w_perc[ow];
     }
     col.forward(S(precip), S(pet));
     settle_load(precip_ahead); settle_load(pet_ahead); settle_load(wr_ahead); settle_load(wp_ahead);

@@ -187,15 +187,28 @@ class LgarEngine:
         """Free the series buffers forward() keeps behind basin sums (they come back on the next such call)."""
         self._basin_scratch = (0, {})
 
-    def _forcing(self, precip, pet, forcing_group):
+    def _forcing(self, precip, pet, forcing_group, forcing_map=None):
         """The forcing pair on the device in the engine's dtype ([T, Nf]; a 1-D pair is one row), checked, with LgarDims'
-        per-call fields (n_steps and the forcing layout) set for it."""
+        per-call fields (n_steps and the forcing layout) set for it.  forcing_map: a forcing.ForcingMap -- the pair is then
+        [T, B] for the map's B forcing columns and the map has one entry per group of forcing_group columns."""
         precip = torch.as_tensor(precip).to(self.device, self.dtype).contiguous()
         pet = torch.as_tensor(pet).to(self.device, self.dtype).contiguous()
         if precip.dim() == 1:
             precip, pet = precip[None, :], pet[None, :]
         g = max(1, int(forcing_group))
-        if (precip.shape != pet.shape or precip.dim() != 2 or precip.shape[1] < 1 or self.N % g != 0
+        if forcing_map is not None:
+            fm = forcing_map
+            index = getattr(fm, "index", None)
+            if (not isinstance(index, torch.Tensor) or index.device != self.status.device or index.dtype != torch.int32
+                    or index.dim() != 1 or not index.is_contiguous() or index.numel() != getattr(fm, "M", None)):
+                raise LgarError("forcing_map must be a ForcingMap on %s (same device as the engine)" % (self.device,))
+            if self.N % g != 0 or fm.M != self.N // g:
+                raise LgarError("forcing_map has %d entries, this engine needs %d: one per group of forcing_group = %d of its "
+                                "%d columns" % (fm.M, self.N // g if self.N % g == 0 else -1, g, self.N))
+            if precip.shape != pet.shape or precip.dim() != 2 or precip.shape[1] != fm.B:
+                raise LgarError("forcing must be [T, %d], one column per forcing column of the forcing_map; got %s / %s"
+                                % (fm.B, tuple(precip.shape), tuple(pet.shape)))
+        elif (precip.shape != pet.shape or precip.dim() != 2 or precip.shape[1] < 1 or self.N % g != 0
                 or (self.N // g) % precip.shape[1] != 0):
             raise LgarError("forcing must be [T, %d] (or [T, Nf] with forcing_group * Nf dividing it: column c reads forcing "
                             "column (c // forcing_group) %% Nf); got %s / %s, forcing_group %d"
@@ -227,10 +240,14 @@ class LgarEngine:
         return scratch
 
     def forward(self, precip, pet, series=("runoff", "percolation"), out=None, check=True, basin=(), weights=None,
-                call_sums=False, forcing_group=1, catchments=None, catchment=()):
+                call_sums=False, forcing_group=1, catchments=None, catchment=(), forcing_map=None):
         """Advance every column by T forcing steps.  precip/pet: [T, N] cm/h on self.device, or [T, Nf] with Nf dividing N
         (broadcast: column c reads forcing column c % Nf; Nf = 1 is one basin series for every column); with forcing_group
         G > 1, G consecutive columns share a forcing column: column c reads (c // G) % Nf.
+        forcing_map: a forcing.ForcingMap (CatchmentMap.forcing_map() makes one) -- precip/pet are then [T, B] for ANY B and
+        column c reads forcing column forcing_map.index[c // G]: catchments of unequal size, each with its own series, and
+        no gathered [T, N] forcing (LgarForcing.column_map, include/lgar.h).  The results are bit for bit those of the
+        gathered forcing precip[:, index].
 
         Returns {name: tensor[T, N]} for the requested per-step series (the model accumulators as they
         stand after each forward(), before MassBalance.change_mass zeroes them).  basin: names whose per-step sum over
@@ -249,7 +266,7 @@ class LgarEngine:
         that is not in `series` gets a scratch series by the rule above; past the budget this raises (there is no in-kernel
         catchment sum)."""
         self._need_state()
-        precip, pet = self._forcing(precip, pet, forcing_group)
+        precip, pet = self._forcing(precip, pet, forcing_group, forcing_map)
         T = precip.shape[0]
         res = {}
         for nm in series:
@@ -290,7 +307,7 @@ class LgarEngine:
         if call_sums:
             res["call_sums"] = torch.zeros(NACC, self.N, dtype=self.dtype, device=self.device)
         so = self._step_out(stored, block, basin, w, res.get("call_sums"))
-        fo = _capi.LgarForcing(precip.data_ptr(), pet.data_ptr())
+        fo = _capi.LgarForcing(precip.data_ptr(), pet.data_ptr(), None if forcing_map is None else forcing_map.index.data_ptr())
         self._call("forward", C.byref(self.dims), C.byref(self._params), C.byref(self._state), C.byref(fo), C.byref(so),
                    self.status.data_ptr())
         if catchments is not None:
@@ -347,19 +364,23 @@ class LgarEngine:
         if bool((status_host != 0).any()):
             self.check_status()
 
-    def tangent(self, direction, precip, pet, w_runoff=None, w_perc=None, want_series=False, forcing_group=1, share=0):
+    def tangent(self, direction, precip, pet, w_runoff=None, w_perc=None, want_series=False, forcing_group=1, share=0,
+                forcing_map=None):
         """Forward-mode tangent from a FRESH state (set_internal_states) over the whole forcing series.
 
         direction: {"alpha" | "n" | "ksat": [L, N] tensor} -- the parameter perturbation (missing = 0).
         precip / pet / w_runoff / w_perc: [T, N], or all [T, Nf] with forcing_group * Nf dividing N (column c uses column
         (c // forcing_group) % Nf of each).
+        forcing_map: a forcing.ForcingMap -- precip / pet are [T, B] and column c reads forcing column
+        forcing_map.index[c // forcing_group]; the weights are then [T, N // forcing_group] and column c reads weight column
+        c // forcing_group (they do not go through the map: the gradient of a catchment sum carries every column's own weight).
         share = W (2..32): each group of W consecutive columns is ONE soil column along W directions; the W lanes share the
         Geff trapezoid (LgarDims.tangent_share).
         Returns (grad[N], tangent_runoff[T, N] or None, status[N]) with
         grad[c] = sum_t w_runoff[t, c] * d runoff_t[c] + w_perc[t, c] * d percolation_t[c].  status != 0 marks columns whose
         tangent integration faulted (their grad entry is not a gradient): callers must check it (autograd.parameter_vjp does)."""
         prep = lambda t: None if t is None else torch.as_tensor(t).to(self.device, self.dtype).contiguous()
-        precip, pet = self._forcing(precip, pet, forcing_group)
+        precip, pet = self._forcing(precip, pet, forcing_group, forcing_map)
         w_runoff, w_perc = prep(w_runoff), prep(w_perc)
         share = int(share)
         if share != 0 and (not 2 <= share <= 32 or self.N % share != 0):
@@ -376,7 +397,11 @@ class LgarEngine:
                                 "multiple of it, or one forcing column for all)" % share)
         self.dims.tangent_share = int(share)
         for nm, w in (("w_runoff", w_runoff), ("w_perc", w_perc)):
-            if w is not None and w.shape != precip.shape:
+            if forcing_map is not None:
+                if w is not None and tuple(w.shape) != (precip.shape[0], forcing_map.M):
+                    raise LgarError("%s must be [T, %d], one column per entry of the forcing_map; got %s"
+                                    % (nm, forcing_map.M, tuple(w.shape)))
+            elif w is not None and w.shape != precip.shape:
                 raise LgarError("%s must be [T, N] like the forcing; got %s" % (nm, tuple(w.shape)))
         T = precip.shape[0]
         dirs = {k: prep(direction.get(k)) for k in ("alpha", "n", "ksat")}
@@ -388,7 +413,7 @@ class LgarEngine:
         ser = self._new_series(T, self.N, dtype=self.dtype, device=self.device) if want_series else None
         st = torch.zeros(self.N, dtype=torch.int32, device=self.device)
         tickets = torch.zeros(_capi.NTICKETS, dtype=torch.int32, device=self.device)  # persistent-wave work counters
-        fo = _capi.LgarForcing(precip.data_ptr(), pet.data_ptr())
+        fo = _capi.LgarForcing(precip.data_ptr(), pet.data_ptr(), None if forcing_map is None else forcing_map.index.data_ptr())
         self._call("forward_tangent", C.byref(self.dims), C.byref(self._params), C.byref(dstruct), C.byref(fo), _ptr(w_runoff),
                    _ptr(w_perc), grad.data_ptr(), _ptr(ser), st.data_ptr(), counters=tickets)
         return grad, ser, st
@@ -491,7 +516,7 @@ class LgarEngine:
         return out if sums is None else (out, sums)
 
     def run_with_soil_moisture(self, precip, pet, every, edges=None, what="theta", series=("runoff", "percolation"), basin=(),
-                               weights=None, check=True, forcing_group=1):
+                               weights=None, check=True, forcing_group=1, forcing_map=None):
         """forward() over the whole forcing with a soil-moisture snapshot after every `every` rows: the run is cut into windows
         of `every` rows, each advanced by forward() on the row slice (series written straight into [T, N] buffers, basin rows
         concatenated), and soil_moisture(edges, what) is taken after each full window.  Returns what forward() returns plus
@@ -500,12 +525,12 @@ class LgarEngine:
         forcing bit for bit.  So are the run totals: forward() adds a call's own sum to them, which over several windows is
         another summation order, so the windows also store the accumulators that feed the totals (scratch series of `every`
         rows for those the caller did not ask for) and lgar_totals_replay adds them up in the one-call order (include/lgar.h;
-        exact for every column that stays in one kernel of the front-capacity chain)."""
+        exact for every column that stays in one kernel of the front-capacity chain).  forcing_map: as in forward()."""
         every = int(every)
         if every < 1:
             raise LgarError("every must be >= 1")
         e_dev, D = self._moisture_bins(edges, what)
-        precip, pet = self._forcing(precip, pet, forcing_group)
+        precip, pet = self._forcing(precip, pet, forcing_group, forcing_map)
         T = precip.shape[0]
         series = tuple(series)
         # (zeros: a row no kernel writes -- a column that had faulted before the window -- must read zero in the replay)
@@ -525,7 +550,7 @@ class LgarEngine:
             out = {nm: res[nm][lo:hi] for nm in series}
             out.update({nm: buf[:hi - lo] for nm, buf in scratch.items()})
             o = self.forward(precip[lo:hi], pet[lo:hi], series=series + tuple(scratch), out=out, check=False, basin=basin,
-                             weights=weights, forcing_group=forcing_group)
+                             weights=weights, forcing_group=forcing_group, forcing_map=forcing_map)
             for nm in basin:
                 rows[nm].append(o["basin:" + nm])
             stored = self._step_out({nm: out[nm] for nm in summed})
