@@ -301,6 +301,46 @@ int32_t lgar_catchment_spread(const double *grad, int32_t n_rows, int32_t n_catc
                               int32_t n_columns, const void *weights, const int32_t *status, void *out, int32_t dtype,
                               void *stream);
 
+/* Catchment routing: one unit hydrograph per catchment over a [n_rows][n_catchments] matrix of catchment sums (what a catchment
+ * job compares with observations is routed runoff at the outlet).  Routing is linear, so it commutes with the catchment sum
+ * and is applied after lgar_catchment_sums; the in-kernel GIUH of the forward kernels (LgarDims.giuh, one hydrograph shared by
+ * every column, at most LGAR_GMAX ordinates; the reference's lgar/giuh.py:8-20) is not touched.
+ *
+ * All arrays are fp64, catchment fastest: x[T][B] the input, ordinates g[K][B] (per_catchment != 0) or g[K] (shared by all
+ * catchments), 1 <= K <= LGAR_ROUTE_KMAX, queue_in / queue_out [K][B]: the carried queue, with the layout and meaning of the
+ * reference's giuh_runoff_queue (queue_in == NULL: zeros; queue_out == NULL: not wanted).  For every catchment b independently,
+ * for t = 0 .. T - 1:
+ *     q[i] <- q[i] + g[i][b] * x[t][b]    i = 0 .. K - 1   (one rounded product, one rounded add: -ffp-contract=off)
+ *     y[t][b] = q[0]
+ *     q[i] <- q[i + 1] for i < K - 1;  q[K - 1] <- +0.0
+ * and queue_out is q after row T - 1.  The kernels evaluate the equivalent statement without a dependence between rows (the
+ * same bits: every y is the same chain of adds, oldest term first):
+ *     y[t][b] starts from queue_in[t][b] if t < K, else from +0.0, and adds g[k][b] * x[t - k][b] for k = min(t, K - 1) down to 0;
+ *     queue_out[i][b] is the same fold for the virtual row T + i over k = K - 1 .. i + 1 with T + i - k >= 0, starting from
+ *     queue_in[T + i][b] when T + i < K.
+ * There is NO skip test: the reference's `sum(queue) > 0 or runoff > 0` changes no value for non-negative input, and without
+ * it the operator is plainly linear, which the adjoint needs.  T = 0 gives queue_out = queue_in; B = 0 is a no-op.  y and
+ * queue_out are WRITTEN, not added to, and the caller zeroes nothing; the result for catchment b depends only on column b of
+ * the inputs -- not on B, on the launch shape or on the run.
+ * RESOLUTION: the operator works at the row resolution of the stored series.  With num_subcycles > 1 the in-kernel GIUH
+ * shifts once per SUB-step, so this is then a different operator from the in-kernel one.
+ *
+ * reverse != 0: the same fold under t -> T - 1 - t on input and output, with a zero queue (queue_in and queue_out must be NULL):
+ *     y[t][b] = the fold of g[k][b] * x[t + k][b] from k = min(K - 1, T - 1 - t) down to 0, starting at +0.0
+ * which is the adjoint of the routing with respect to x (x holds the gradient of y, y receives the gradient of x).
+ * K outside 1 .. LGAR_ROUTE_KMAX, negative sizes, or a null x (with T, B > 0), y (T, B > 0) or ordinates return LGAR_E_ARG. */
+#define LGAR_ROUTE_KMAX 64
+int32_t lgar_catchment_route(const double *x, int32_t n_rows, int32_t n_catchments, const double *ordinates,
+                             int32_t n_ordinates, int32_t per_catchment, const double *queue_in, double *queue_out, double *y,
+                             int32_t reverse, void *stream);
+
+/* Gradient of the routing with respect to the ordinates, per catchment:
+ *     g_out[k][b] = sum over t = k .. T - 1 of gy[t][b] * x[t - k][b]
+ * from +0.0, in increasing t, with plain fp64 products and adds.  Rows before the call (the carried queue) are constants.
+ * g_out: [n_ordinates][n_catchments], written; for shared ordinates the caller sums it over b. */
+int32_t lgar_catchment_route_grad(const double *x, const double *gy, int32_t n_rows, int32_t n_catchments,
+                                  int32_t n_ordinates, double *g_out, void *stream);
+
 /* Run totals of a run cut into several lgar_forward calls.  lgar_forward sums a call's accumulators step by step from zero
  * and adds that sum to LgarState.totals, so a chunked run adds several partial sums where one call adds one: the same numbers in
  * another order, equal to the last bits only.  This replays the one-call order over series the chunks stored: for every j < 7

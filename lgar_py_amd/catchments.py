@@ -5,6 +5,10 @@ weighted); what is compared with observations is catchment runoff.  CatchmentMap
 map of lgar_catchment_sums (include/lgar.h; DESIGN.md section 10 has the definition), once, and runs the two kernels of
 csrc/lgar_catchment.hip over device tensors.  There is no CPU fallback: a map can be BUILT for device="cpu" (its host logic
 needs no GPU), sums() and spread() need the library and a GPU.
+
+CatchmentRouting routes such a [T, B] matrix through one unit hydrograph per catchment (lgar_catchment_route, include/lgar.h;
+DESIGN.md section 12), with the adjoint and the gradient with respect to the ordinates; catchment_route is the differentiable
+form.
 """
 import ctypes as C
 
@@ -182,3 +186,155 @@ def catchment_sum(series, cmap, status=None):
     autograd.lgar_series (parameters -> runoff [T, N] -> catchment runoff [T, B] -> loss) and with the graph-connected blocks
     model.dpLGAR returns."""
     return _CatchmentSum.apply(series, cmap, status)
+
+
+class CatchmentRouting:
+    """One unit hydrograph per catchment over a [T, B] matrix of catchment sums (lgar_catchment_route, include/lgar.h; DESIGN.md
+    section 12 has the definition: the reference's GIUH queue, lgar/giuh.py:8-20, without its skip test).
+
+    ordinates: [K] (one hydrograph shared by all catchments) or [B, K] (one per catchment; kept transposed, [K, B], on the
+    device), finite, 1 <= K <= 64 (LGAR_ROUTE_KMAX).  n_catchments: B; required for nothing -- shared ordinates take B from the
+    first matrix routed -- but a [B', K] that does not match it is refused.  The operator works at the row resolution of the
+    series it is given: with num_subcycles > 1 the in-kernel GIUH shifts once per sub-step and is a different operator.
+    There is no CPU fallback: the object can be BUILT for device="cpu" (its host logic needs no GPU), route(), adjoint() and
+    ordinate_grad() need the library and a GPU."""
+
+    def __init__(self, ordinates, n_catchments=None, device="cuda:0"):
+        try:
+            g = ordinates if isinstance(ordinates, torch.Tensor) else torch.from_numpy(np.asarray(ordinates, dtype=np.float64))
+            g = g.detach().to("cpu", torch.float64)
+        except (TypeError, ValueError, RuntimeError) as err:
+            raise LgarError("ordinates must be [K] or [B, K] numbers (%s)" % err)
+        if g.dim() not in (1, 2):
+            raise LgarError("ordinates must be [K] (shared) or [B, K] (one hydrograph per catchment); got shape %s" % (tuple(g.shape),))
+        K = int(g.shape[-1])
+        if not 1 <= K <= _capi.ROUTE_KMAX:
+            raise LgarError("a hydrograph has 1 .. %d ordinates (got %d)" % (_capi.ROUTE_KMAX, K))
+        if not bool(torch.isfinite(g).all()):
+            raise LgarError("ordinates must be finite")
+        self.per_catchment = g.dim() == 2
+        B = None if n_catchments is None else int(n_catchments)
+        if B is not None and not 0 <= B < 2 ** 31:
+            raise LgarError("n_catchments must be in 0 .. 2^31 - 1 (got %d)" % B)
+        if self.per_catchment:
+            if B is not None and int(g.shape[0]) != B:
+                raise LgarError("ordinates are [%d, %d]: one hydrograph for each of %d catchments, not %d" % (g.shape[0], K, g.shape[0], B))
+            B = int(g.shape[0])
+            g = g.t()
+        self.K, self.B = K, B
+        self.ordinates_host = g.contiguous()  # [K] or [K, B]
+        self.device = torch.device(device)
+        self.ordinates = self.ordinates_host.to(self.device)
+        self._queues = {}  # key -> [K, B] carried queue (absent: zeros)
+
+    # ------------------------------------------------------------------------------------------
+    def _lib(self):
+        if self.device.type != "cuda" or not torch.cuda.is_available():
+            raise LgarError("catchment routing runs on a ROCm GPU: there is no CPU fallback (routing device %s)" % (self.device,))
+        return _capi.load()
+
+    def _matrix(self, x, what):
+        if (not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float64 or x.device != self.ordinates.device
+                or (self.B is not None and x.shape[1] != self.B)):
+            raise LgarError("%s must be a fp64 [T, %s] tensor on %s" % (what, "B" if self.B is None else self.B, self.device))
+        if x.shape[0] >= 2 ** 31 or x.shape[1] >= 2 ** 31:
+            raise LgarError("at most 2^31 - 1 rows and catchments")
+        return x.detach().contiguous()
+
+    def _route(self, x, queue_in, want_queue, reverse):
+        lib = self._lib()
+        T, B = int(x.shape[0]), int(x.shape[1])
+        y = torch.empty(T, B, dtype=torch.float64, device=self.device)
+        queue_out = torch.empty(self.K, B, dtype=torch.float64, device=self.device) if want_queue else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with torch.cuda.device(self.device):
+            rc = lib.lgar_catchment_route(x.data_ptr(), T, B, self.ordinates.data_ptr(), self.K, int(self.per_catchment),
+                                          ptr(queue_in), ptr(queue_out), y.data_ptr(), int(reverse), stream)
+        _capi.check(rc, "lgar_catchment_route")
+        return y, queue_out
+
+    def _queue_arg(self, queue, B):
+        if queue is None:
+            return None
+        if (not isinstance(queue, torch.Tensor) or tuple(queue.shape) != (self.K, B) or queue.dtype != torch.float64
+                or queue.device != self.ordinates.device):
+            raise LgarError("queue must be a fp64 [%d, %d] tensor on %s" % (self.K, B, self.device))
+        return queue.detach().contiguous()
+
+    def route(self, x, carry=True, key=None, queue=None):
+        """x: fp64 [T, B] on the routing's device -> fp64 [T, B], routed.  carry=True: the [K, B] queue stays on the device
+        between calls, as an engine keeps its state: chunked calls equal one call bit for bit (one queue per `key`: an engine
+        that routes several series through one routing keeps them apart by name); `queue` (a [K, B] tensor) replaces the carried
+        queue first: a run resumed from a stored one.  carry=False: starts from `queue` (or None = zeros) and keeps nothing."""
+        x = self._matrix(x, "x")
+        if carry:
+            q = self._queues.get(key) if queue is None else self._queue_arg(queue, int(x.shape[1]))
+            if q is not None and q.shape[1] != x.shape[1]:
+                raise LgarError("the carried queue is [%d, %d]: x must keep its %d catchments (reset() starts anew)" % (self.K, q.shape[1], q.shape[1]))
+            y, self._queues[key] = self._route(x, q, True, False)
+            return y
+        return self._route(x, self._queue_arg(queue, int(x.shape[1])), False, False)[0]
+
+    def reset(self):
+        """Empty every carried queue."""
+        self._queues = {}
+
+    def queue_of(self, key=None):
+        """The carried [K, B] queue of `key` (the layout and meaning of the reference's giuh_runoff_queue), or None before the
+        first carried call."""
+        return self._queues.get(key)
+
+    queue = property(queue_of)
+
+    def adjoint(self, gy):
+        """The adjoint of route() with respect to x (a zero queue): gy fp64 [T, B] -> gx [T, B],
+        gx[t] = the fold of g[k] * gy[t + k] from k = min(K - 1, T - 1 - t) down to 0 -- the same kernel under t -> T - 1 - t."""
+        return self._route(self._matrix(gy, "gy"), None, False, True)[0]
+
+    def ordinate_grad(self, x, gy):
+        """The gradient of sum(gy * route(x)) with respect to the ordinates, in their own shape: [B, K] per catchment,
+        gg[b, k] = sum_{t >= k} gy[t, b] * x[t - k, b] in increasing t (a fixed order); for shared ordinates that [B, K] result
+        is summed over b with torch, and THAT sum is not order-pinned (its last bits may differ between runs).  The carried
+        queue is a constant."""
+        lib = self._lib()
+        x, gy = self._matrix(x, "x"), self._matrix(gy, "gy")
+        if x.shape != gy.shape:
+            raise LgarError("x and gy must have one shape (got %s and %s)" % (tuple(x.shape), tuple(gy.shape)))
+        T, B = int(x.shape[0]), int(x.shape[1])
+        out = torch.empty(self.K, B, dtype=torch.float64, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with torch.cuda.device(self.device):
+            rc = lib.lgar_catchment_route_grad(x.data_ptr(), gy.data_ptr(), T, B, self.K, out.data_ptr(), stream)
+        _capi.check(rc, "lgar_catchment_route_grad")
+        return out.t().contiguous() if self.per_catchment else out.sum(dim=1)
+
+
+class _CatchmentRoute(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, ordinates, routing, queue):
+        ctx.routing, ctx.g_dtype = routing, None if ordinates is None else ordinates.dtype
+        ctx.save_for_backward(x)
+        return routing.route(x, carry=False, queue=queue)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, = ctx.saved_tensors
+        gy = gy.contiguous()
+        gx = ctx.routing.adjoint(gy) if ctx.needs_input_grad[0] else None
+        gg = ctx.routing.ordinate_grad(x, gy).to(ctx.g_dtype) if ctx.needs_input_grad[1] else None
+        return gx, gg, None, None
+
+
+def catchment_route(x, routing_or_ordinates, queue=None):
+    """Differentiable routing: fp64 [T, B] -> [T, B].  routing_or_ordinates: a CatchmentRouting (its ordinates are constants),
+    or an ordinates tensor [K] / [B, K], which gets a gradient when it requires one (CatchmentRouting.ordinate_grad).  The
+    backward pass with respect to x is CatchmentRouting.adjoint.  No stateful queue is used or kept: the routing starts from
+    `queue` ([K, B], a constant) or from zeros.  Composes with catchment_sum and autograd.lgar_series (parameters -> runoff
+    [T, N] -> catchment runoff [T, B] -> routed runoff -> loss)."""
+    if isinstance(routing_or_ordinates, CatchmentRouting):
+        return _CatchmentRoute.apply(x, None, routing_or_ordinates, queue)
+    if not isinstance(routing_or_ordinates, torch.Tensor):
+        raise LgarError("catchment_route takes a CatchmentRouting or an ordinates tensor ([K] or [B, K])")
+    routing = CatchmentRouting(routing_or_ordinates, n_catchments=int(x.shape[1]) if x.dim() == 2 else None, device=x.device)
+    return _CatchmentRoute.apply(x, routing_or_ordinates, routing, queue)

@@ -240,7 +240,7 @@ class LgarEngine:
         return scratch
 
     def forward(self, precip, pet, series=("runoff", "percolation"), out=None, check=True, basin=(), weights=None,
-                call_sums=False, forcing_group=1, catchments=None, catchment=(), forcing_map=None):
+                call_sums=False, forcing_group=1, catchments=None, catchment=(), forcing_map=None, routing=None):
         """Advance every column by T forcing steps.  precip/pet: [T, N] cm/h on self.device, or [T, Nf] with Nf dividing N
         (broadcast: column c reads forcing column c % Nf; Nf = 1 is one basin series for every column); with forcing_group
         G > 1, G consecutive columns share a forcing column: column c reads (c // G) % Nf.
@@ -264,7 +264,11 @@ class LgarEngine:
         taken from the stored series after the launch (lgar_catchment_sums, include/lgar.h: a fixed summation order per
         catchment, the same bits on every run) with the engine's status, so a faulted column drops out of every row.  A name
         that is not in `series` gets a scratch series by the rule above; past the budget this raises (there is no in-kernel
-        catchment sum)."""
+        catchment sum).
+        routing: a catchments.CatchmentRouting over the map's B catchments: every name in `catchment` is also returned routed
+        through it, "catchment:routed:<name>" (fp64 [T, B]), on the same stream, with the routing's queue of that name carried
+        from call to call as the engine carries its state (lgar_catchment_route, include/lgar.h: at the row resolution of the
+        stored series; routing.reset() goes with reset()).  routing needs catchments."""
         self._need_state()
         precip, pet = self._forcing(precip, pet, forcing_group, forcing_map)
         T = precip.shape[0]
@@ -304,6 +308,11 @@ class LgarEngine:
                                         % (nm, T, self.N, self.basin_scratch_bytes))
         elif catchment:
             raise LgarError("catchment=%r needs catchments=<CatchmentMap>" % (tuple(catchment),))
+        if routing is not None:
+            if catchments is None:
+                raise LgarError("routing needs catchments=<CatchmentMap>: it routes the [T, B] catchment sums")
+            if getattr(routing, "B", None) not in (None, catchments.B) or routing.ordinates.device != self.status.device:
+                raise LgarError("routing must be a CatchmentRouting over the map's %d catchments on %s" % (catchments.B, self.device))
         if call_sums:
             res["call_sums"] = torch.zeros(NACC, self.N, dtype=self.dtype, device=self.device)
         so = self._step_out(stored, block, basin, w, res.get("call_sums"))
@@ -317,6 +326,9 @@ class LgarEngine:
                 res["catchment:" + nm] = catchments.sums(stored[nm], status=self.status)
             no_rows = torch.empty(0, self.N, dtype=self.dtype, device=self.device)
             res["catchment:weight"] = catchments.sums(no_rows, status=self.status, weight_sums=True)[1]
+            if routing is not None:
+                for nm in catchment:
+                    res["catchment:routed:" + nm] = routing.route(res["catchment:" + nm], carry=True, key=nm)
         if check:
             self.check_status()
         return res
