@@ -1,10 +1,13 @@
 """ctypes binding of the C-ABI declared in include/lgar.h (liblgar_hip.so).
 
 There is no CPU fallback: if the HIP library is missing or cannot be loaded, every entry point
-raises.  Torch is used only for device memory and streams; the signatures carry raw pointers.
+raises.  Torch is used only for device memory and streams; the signatures carry raw pointers.  open_library and launch are
+the one way into the library: every entry point the package calls goes through them.
 """
 import ctypes as C
 import os
+
+import torch
 
 from . import build as _build
 
@@ -157,3 +160,38 @@ def check(rc, what):
     if rc != 0:
         raise LgarError("%s failed with code %d (%s)" % (what, rc, {-1: "bad argument", -2: "launch error",
                                                                      -3: "no device"}.get(rc, "?")))
+
+
+def ptr(t):
+    """The address a tensor's data starts at; None (a null pointer) for None."""
+    return None if t is None else t.data_ptr()
+
+
+def dtype_code(dtype, what):
+    """LGAR_F32 / LGAR_F64 of a torch dtype; any other dtype raises `what` (the caller's message)."""
+    if dtype == torch.float64:
+        return F64
+    if dtype == torch.float32:
+        return F32
+    raise LgarError(what)
+
+
+def open_library(device, what):
+    """The loaded library for a ROCm device; anything else raises `what` (a message with one %s for the device): there is no
+    CPU fallback."""
+    if torch.device(device).type != "cuda" or not torch.cuda.is_available():
+        raise LgarError(what % (device,))
+    return load()
+
+
+def launch(lib, name, device, *args, tail=()):
+    """Entry point lgar_<name> of `lib` on `device` and its current stream: `args`, then the stream, then `tail` (what the
+    header puts behind the stream: lgar_forward_tangent's tickets).  A non-zero return raises.  A library that stands in for
+    the HIP library on another device (open_library gives none: a test's host build of the device code) gets a null stream."""
+    fn = getattr(lib, "lgar_" + name)
+    if device.type != "cuda":
+        rc = fn(*args, None, *tail)
+    else:
+        with torch.cuda.device(device):
+            rc = fn(*args, C.c_void_p(torch.cuda.current_stream(device).cuda_stream), *tail)
+    check(rc, "lgar_" + name)

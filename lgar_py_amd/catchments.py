@@ -10,22 +10,15 @@ CatchmentRouting routes such a [T, B] matrix through one unit hydrograph per cat
 DESIGN.md section 12), with the adjoint and the gradient with respect to the ordinates; catchment_route is the differentiable
 form.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _capi
-from ._capi import LgarError
+from ._capi import LgarError, ptr
 from .forcing import ForcingMap
 
 
-def _dtype_code(dtype):
-    if dtype == torch.float64:
-        return _capi.F64
-    if dtype == torch.float32:
-        return _capi.F32
-    raise LgarError("catchment sums take float32 or float64 (got %s)" % (dtype,))
+_DTYPES = "catchment sums take float32 or float64 (got %s)"
 
 
 class CatchmentMap:
@@ -102,10 +95,9 @@ class CatchmentMap:
         return self._forcing_map
 
     # ------------------------------------------------------------------------------------------
-    def _lib(self):
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise LgarError("catchment sums run on a ROCm GPU: there is no CPU fallback (map device %s)" % (self.device,))
-        return _capi.load()
+    def _open(self):
+        """The library sums() and spread() run on (what the test suite's device-code simulator replaces)."""
+        return _capi.open_library(self.device, "catchment sums run on a ROCm GPU: there is no CPU fallback (map device %s)")
 
     def _status(self, status):
         if status is None:
@@ -123,11 +115,11 @@ class CatchmentMap:
         rows hold.  out: optional contiguous fp64 [R, B] buffer; it is written, not added to.  weight_sums=True: returns
         (sums, fp64 [B] sums of the weights of the members that were not skipped) -- sums / weight_sums is the mean over the
         valid columns."""
-        lib = self._lib()
+        lib = self._open()
         if (not isinstance(series, torch.Tensor) or series.dim() != 2 or series.shape[1] != self.N
                 or series.device != self.ids.device or not series.is_contiguous()):
             raise LgarError("series must be a contiguous [R, %d] tensor on %s" % (self.N, self.device))
-        code = _dtype_code(series.dtype)
+        code = _capi.dtype_code(series.dtype, _DTYPES % (series.dtype,))
         R = int(series.shape[0])
         if R >= 2 ** 31:
             raise LgarError("at most 2^31 - 1 rows")
@@ -139,21 +131,17 @@ class CatchmentMap:
             raise LgarError("out must be a contiguous fp64 [%d, %d] tensor on %s" % (R, self.B, self.device))
         wsum = torch.empty(self.B, dtype=torch.float64, device=self.device) if weight_sums else None
         w = self.weights(series.dtype)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            rc = lib.lgar_catchment_sums(series.data_ptr(), R, self.N, self.offsets.data_ptr(), self.B, ptr(self.order),
-                                         0 if self.order is None else int(self.order.numel()), ptr(w), ptr(status),
-                                         out.data_ptr(), ptr(wsum), code, stream)
-        _capi.check(rc, "lgar_catchment_sums")
+        _capi.launch(lib, "catchment_sums", self.device, series.data_ptr(), R, self.N, self.offsets.data_ptr(), self.B,
+                     ptr(self.order), 0 if self.order is None else int(self.order.numel()), ptr(w), ptr(status), out.data_ptr(),
+                     ptr(wsum), code)
         return (out, wsum) if weight_sums else out
 
     def spread(self, grad, dtype, status=None):
         """The adjoint of sums(): grad [R, B] (converted to fp64) -> [R, N] tensor of `dtype`,
         out[r, c] = grad[r, ids[c]] * weight[c] rounded once to dtype; 0 for columns of no catchment and for columns whose
         status has a fault bit.  What LgarEngine.tangent / autograd.parameter_vjp take as w_runoff / w_perc."""
-        lib = self._lib()
-        code = _dtype_code(dtype)
+        lib = self._open()
+        code = _capi.dtype_code(dtype, _DTYPES % (dtype,))
         if not isinstance(grad, torch.Tensor) or grad.dim() != 2 or grad.shape[1] != self.B:
             raise LgarError("grad must be a [R, %d] tensor" % self.B)
         grad = grad.detach().to(self.device, torch.float64).contiguous()
@@ -161,12 +149,8 @@ class CatchmentMap:
         status = self._status(status)
         out = torch.empty(R, self.N, dtype=dtype, device=self.device)
         w = self.weights(dtype)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            rc = lib.lgar_catchment_spread(grad.data_ptr(), R, self.B, self.ids.data_ptr(), self.N, ptr(w), ptr(status),
-                                           out.data_ptr(), code, stream)
-        _capi.check(rc, "lgar_catchment_spread")
+        _capi.launch(lib, "catchment_spread", self.device, grad.data_ptr(), R, self.B, self.ids.data_ptr(), self.N, ptr(w),
+                     ptr(status), out.data_ptr(), code)
         return out
 
 
@@ -228,10 +212,9 @@ class CatchmentRouting:
         self._queues = {}  # key -> [K, B] carried queue (absent: zeros)
 
     # ------------------------------------------------------------------------------------------
-    def _lib(self):
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise LgarError("catchment routing runs on a ROCm GPU: there is no CPU fallback (routing device %s)" % (self.device,))
-        return _capi.load()
+    def _open(self):
+        """The library the routing runs on (what the test suite's device-code simulator replaces)."""
+        return _capi.open_library(self.device, "catchment routing runs on a ROCm GPU: there is no CPU fallback (routing device %s)")
 
     def _matrix(self, x, what):
         if (not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float64 or x.device != self.ordinates.device
@@ -242,16 +225,12 @@ class CatchmentRouting:
         return x.detach().contiguous()
 
     def _route(self, x, queue_in, want_queue, reverse):
-        lib = self._lib()
+        lib = self._open()
         T, B = int(x.shape[0]), int(x.shape[1])
         y = torch.empty(T, B, dtype=torch.float64, device=self.device)
         queue_out = torch.empty(self.K, B, dtype=torch.float64, device=self.device) if want_queue else None
-        ptr = lambda t: None if t is None else t.data_ptr()
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            rc = lib.lgar_catchment_route(x.data_ptr(), T, B, self.ordinates.data_ptr(), self.K, int(self.per_catchment),
-                                          ptr(queue_in), ptr(queue_out), y.data_ptr(), int(reverse), stream)
-        _capi.check(rc, "lgar_catchment_route")
+        _capi.launch(lib, "catchment_route", self.device, x.data_ptr(), T, B, self.ordinates.data_ptr(), self.K,
+                     int(self.per_catchment), ptr(queue_in), ptr(queue_out), y.data_ptr(), int(reverse))
         return y, queue_out
 
     def _queue_arg(self, queue, B):
@@ -297,16 +276,13 @@ class CatchmentRouting:
         gg[b, k] = sum_{t >= k} gy[t, b] * x[t - k, b] in increasing t (a fixed order); for shared ordinates that [B, K] result
         is summed over b with torch, and THAT sum is not order-pinned (its last bits may differ between runs).  The carried
         queue is a constant."""
-        lib = self._lib()
+        lib = self._open()
         x, gy = self._matrix(x, "x"), self._matrix(gy, "gy")
         if x.shape != gy.shape:
             raise LgarError("x and gy must have one shape (got %s and %s)" % (tuple(x.shape), tuple(gy.shape)))
         T, B = int(x.shape[0]), int(x.shape[1])
         out = torch.empty(self.K, B, dtype=torch.float64, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            rc = lib.lgar_catchment_route_grad(x.data_ptr(), gy.data_ptr(), T, B, self.K, out.data_ptr(), stream)
-        _capi.check(rc, "lgar_catchment_route_grad")
+        _capi.launch(lib, "catchment_route_grad", self.device, x.data_ptr(), gy.data_ptr(), T, B, self.K, out.data_ptr())
         return out.t().contiguous() if self.per_catchment else out.sum(dim=1)
 
 

@@ -10,6 +10,7 @@ import torch
 
 from . import _capi
 from ._capi import ACC_NAMES, GMAX, LMAX, LMIN, NACC, NSCAL, LgarError
+from ._capi import ptr as _ptr
 
 BASIN_SCRATCH_BYTES = 8 << 30  # most series memory, over ALL basin names, an engine allocates on its own behind basin sums
 PARAMS = ("alpha", "n", "ksat", "theta_e", "theta_r", "thickness")
@@ -23,13 +24,8 @@ _DIMS_SETTINGS = ("dt_h", "num_subcycles", "initial_psi", "ponded_depth_max", "w
                   "giuh_ordinates", "iter_cap", "search_mode", "bottom_mode", "use_closed_form_G", "forward_lanes")
 
 
-def _require_gpu(device):
-    if not torch.cuda.is_available():
-        raise LgarError("no ROCm GPU visible: the LGAR engine has no CPU fallback (device=%s)" % (device,))
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+_NO_GPU = "no ROCm GPU visible: the LGAR engine has no CPU fallback (device=%s)"
+_DTYPES = "dtype must be torch.float32 or torch.float64"
 
 
 class LgarStatusError(ValueError):
@@ -76,11 +72,8 @@ class LgarEngine:
         if not LMIN <= L <= LMAX:
             raise LgarError("this build supports %d..%d soil layers (got %d)" % (LMIN, LMAX, L))
         self.lib, self.device = self._open(L, s["device"])
-        dtype = s["dtype"]
-        if dtype not in (torch.float32, torch.float64):
-            raise LgarError("dtype must be torch.float32 or torch.float64")
-        self.dtype = dtype
-        self._dt = _capi.F64 if dtype == torch.float64 else _capi.F32
+        dtype = self.dtype = s["dtype"]
+        self._dt = _capi.dtype_code(dtype, _DTYPES)
 
         def prep(x):
             t = torch.as_tensor(x, dtype=torch.float64)
@@ -163,16 +156,12 @@ class LgarEngine:
     def _open(self, n_layers, device):
         """(library, torch.device) this engine runs on."""
         device = torch.device(device)
-        _require_gpu(device)
-        return _capi.load(), device
+        return _capi.open_library(device, _NO_GPU), device
 
     def _call(self, name, *args, counters=None):
         """Entry point lgar_<name> on this engine's device and current stream: `args`, then the dtype code, the stream and, for
         the tangent, its work counters."""
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            rc = getattr(self.lib, "lgar_" + name)(*args, self._dt, stream, *(() if counters is None else (counters.data_ptr(),)))
-        _capi.check(rc, "lgar_" + name)
+        _capi.launch(self.lib, name, self.device, *args, self._dt, tail=() if counters is None else (counters.data_ptr(),))
 
     # ------------------------------------------------------------------------------------------
     def _need_state(self):
@@ -603,17 +592,13 @@ def leaf_batch(op, x, y=None, z=0.0, *, alpha, n, ksat, theta_e, theta_r, nint=1
                dtype=torch.float64, device="cuda:0"):
     """Element-wise leaf kernels (known-answer tests): see lgar_leaf_batch in include/lgar.h."""
     dev = torch.device(device)
-    _require_gpu(dev)
-    lib = _capi.load()
+    lib = _capi.open_library(dev, _NO_GPU)
     ops = {"theta_from_h": 0, "se_from_h": 1, "k_from_se": 2, "h_from_se": 3, "geff": 4, "aet": 5, "geff_literal": 6,
            "log2": 7, "exp2": 8, "pow": 9, "geff_mixed": 10, "div": 11, "pow_pairwise": 12, "log2_pairwise": 13, "exp2_pairwise": 14}
     prep = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float64).to(dev, dtype).contiguous()
     x, y, alpha, n, ksat, theta_e, theta_r = map(prep, (x, y, alpha, n, ksat, theta_e, theta_r))
     out = torch.empty_like(x)
-    with torch.cuda.device(dev):
-        rc = lib.lgar_leaf_batch(ops[op], x.numel(), _ptr(x), _ptr(y), float(z), _ptr(alpha), _ptr(n), _ptr(ksat),
-                                 _ptr(theta_e), _ptr(theta_r), int(nint), float(wilting_point_psi), _ptr(out),
-                                 _capi.F64 if dtype == torch.float64 else _capi.F32,
-                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    _capi.check(rc, "lgar_leaf_batch")
+    _capi.launch(lib, "leaf_batch", dev, ops[op], x.numel(), _ptr(x), _ptr(y), float(z), _ptr(alpha), _ptr(n), _ptr(ksat),
+                 _ptr(theta_e), _ptr(theta_r), int(nint), float(wilting_point_psi), _ptr(out),
+                 _capi.dtype_code(dtype, _DTYPES))
     return out

@@ -1,6 +1,7 @@
 """TEST INFRASTRUCTURE ONLY: the one recipe by which the suite's host builds of the device code (tests/devsim,
-tests/moisture_host, tests/launch_plan) are made with the ROCm clang -- stale by file time, compiled to a temporary name,
-renamed into place (several test workers or threads may build the same output at once)."""
+tests/post_host, tests/launch_plan) are made with the ROCm clang -- stale by file time, compiled to a temporary name,
+renamed into place (several test workers or threads may build the same output at once) -- and the one way their stand-alone
+programs are run."""
 import os
 import subprocess
 import threading
@@ -27,3 +28,12 @@ def build(out, source, deps, flags=(), what="a host build of the device code"):
         subprocess.check_call([CLANG, "-x", "c++", "-std=c++17", "-O1", "-ffp-contract=off"] + list(flags) + [source, "-o", tmp])
         os.replace(tmp, out)
     return out
+
+
+def run_clean(argv):
+    """Run a stand-alone host program (a sanitizer build halts at its first finding) and require a clean exit: status 0,
+    nothing on stderr.  Returns its stdout."""
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    p = subprocess.run(argv, capture_output=True, text=True, env=env, timeout=300)
+    assert p.returncode == 0 and not p.stderr.strip(), (p.returncode, p.stderr[-4000:])
+    return p.stdout

@@ -3,8 +3,9 @@
 The simulator is lgar_py_amd/csrc's device code (column physics, per-lane kernel bodies, front-capacity chain) compiled
 for the host with -DLGAR_DEVSIM, one lane at a time.  SimEngine is the product's LgarEngine with that library in the HIP
 library's place, so CPU tests run the code the GPU executes against the reference's golden vectors, and the product's own
-host code -- argument checks, struct filling, the model, the autograd tape, the agent (install()) -- without a GPU.
-Never imported by the product package; never timed.
+host code -- argument checks, struct filling, the model, the autograd tape, the agent (install()) -- without a GPU.  The
+post-processing entry points (soil moisture, totals replay, catchment sums and routing) come from tests/post_host's library,
+behind SimEngine, SimCatchmentMap and SimCatchmentRouting.  Never imported by the product package; never timed.
 """
 import ctypes as C
 import hashlib
@@ -16,10 +17,12 @@ import numpy as np
 import torch
 
 import _hostbuild
+import post_host
 from _hostbuild import CLANG, CSRC, ROOT  # noqa: F401
 # the one mirror of include/lgar.h (tests/test_capi_host.py checks it against the header)
 from lgar_py_amd import _capi
 from lgar_py_amd._capi import ACC_NAMES, LgarDims, LgarError, LgarForcing, LgarParams, LgarState, LgarStepOut  # noqa: F401
+from lgar_py_amd.catchments import CatchmentMap, CatchmentRouting
 from lgar_py_amd.engine import LgarEngine
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -66,6 +69,30 @@ def prebuild(layers=(2, 3, 4)):
         list(ex.map(lib, layers))
 
 
+class _PostLibrary:
+    """libposthost.so (tests/post_host) under the HIP library's names: lgar_<name>(arguments, stream) is posthost_<name>(arguments).
+    The catchment sums run one row per wave, the kernel the library itself picks for all but huge jobs (the same bits)."""
+
+    def __getattr__(self, name):
+        fn = getattr(post_host.library(), "posthost_" + name[len("lgar_"):])
+        tail = (1,) if name == "lgar_catchment_sums" else ()
+        return lambda *args: fn(*args[:-1], *tail)
+
+
+class SimCatchmentMap(CatchmentMap):
+    """lgar_py_amd.catchments.CatchmentMap (device="cpu") with the host build of the catchment kernels in the library's place."""
+
+    def _open(self):
+        return _PostLibrary()
+
+
+class SimCatchmentRouting(CatchmentRouting):
+    """lgar_py_amd.catchments.CatchmentRouting (device="cpu") with the host build of the routing kernels in the library's place."""
+
+    def _open(self):
+        return _PostLibrary()
+
+
 class SimEngine(LgarEngine):
     """lgar_py_amd.engine.LgarEngine with the simulator in the library's place: torch CPU tensors, the devsim_* entry points.
     Everything about the calling surface is the product's own code.  Also takes numpy dtypes and geff_mode=0|1 for
@@ -88,9 +115,14 @@ class SimEngine(LgarEngine):
         return lib(n_layers), torch.device("cpu")
 
     def _call(self, name, *args, counters=None):
-        fn = getattr(self.lib, "devsim_" + {"forward_tangent": "tangent"}.get(name, name), None)
-        if fn is None:
-            raise LgarError("the device-code simulator has no lgar_%s" % name)
+        if name in ("soil_moisture", "totals_replay"):
+            if name == "soil_moisture":
+                *args, _, basin = args  # (weights belong to the basin sums)
+                if basin is not None:
+                    raise LgarError("the device-code simulator has no basin sums of the soil moisture: the summation order of "
+                                    "lgar_basin_reduce_kernel has no host form")
+            return _capi.launch(_PostLibrary(), name, self.device, *args, self._dt)
+        fn = getattr(self.lib, "devsim_" + {"forward_tangent": "tangent"}.get(name, name))
         _capi.check(fn(*args, self._dt), "devsim: lgar_" + name)
 
     def step_rows_host(self, precip_row, pet_row):

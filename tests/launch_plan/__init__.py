@@ -4,7 +4,6 @@ the host with -DLGAR_DEVSIM.  Never imported by the product package.
 """
 import json
 import os
-import subprocess
 
 import _hostbuild
 
@@ -19,10 +18,7 @@ def program(sanitize=False):
 
 
 def _run(args, sanitize):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    p = subprocess.run([program(sanitize)] + args, capture_output=True, text=True, env=env, timeout=300)
-    assert p.returncode == 0 and not p.stderr.strip(), (p.returncode, p.stderr[-4000:])
-    return [json.loads(line) for line in p.stdout.splitlines()]
+    return [json.loads(line) for line in _hostbuild.run_clean([program(sanitize)] + args).splitlines()]
 
 
 def forward_plans(cases, sanitize=False):

@@ -1,19 +1,11 @@
 """TEST INFRASTRUCTURE ONLY: the numpy statement of the catchment sums (include/lgar.h, lgar_catchment_sums; DESIGN.md section
-10) and the front-end of the stand-alone host program (tests/catchment_host/catchment_host.cpp) that runs
-lgar_py_amd/csrc/lgar_catchment.hpp -- the per-lane accumulation and combine order of the GPU kernel -- compiled for the host
-with -DLGAR_DEVSIM.  Never imported by the product package.
+10), and the calls of the host program (post_host.run) that run lgar_py_amd/csrc/lgar_catchment.hpp -- the per-lane
+accumulation and combine order of the GPU kernel -- over the same data.  Never imported by the product package.
 """
-import os
-import struct
-import subprocess
-import tempfile
-
 import numpy as np
 
-import _hostbuild
-from _hostbuild import CSRC, ROOT
+from post_host import Out, dtype_code, same_bits  # noqa: F401
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
 FAULT_MASK = 0x7F  # LGAR_ST_FAULT_MASK
 SIZES = (0, 1, 63, 64, 65, 255, 256, 257, 1000)  # members per catchment: around the lane count and the partial count; N = 2121
 # ... and beyond 1024 members, where a lane of the one-row kernel takes whole blocks of 16 loads (1024 members a block): two
@@ -104,72 +96,22 @@ def csr_of(ids, B):
     return offsets, order
 
 
-def same_bits(a, b):
-    """Bit-for-bit equality of two float arrays (NaNs must sit in the same places)."""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    u = np.uint64 if a.dtype == np.float64 else np.uint32
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool((na == nb).all() and (a.view(u)[~na] == b.view(u)[~nb]).all())
-
-
-def program(sanitize=False):
-    """The host program, built on first use with the ROCm clang (sanitize: AddressSanitizer + UBSan, any finding aborts)."""
-    return _hostbuild.build(os.path.join(_HERE, "catchment_host_san" if sanitize else "catchment_host"),
-                            os.path.join(_HERE, "catchment_host.cpp"),
-                            [os.path.join(CSRC, "lgar_catchment.hpp"), os.path.join(ROOT, "include", "lgar.h")],
-                            _hostbuild.SANITIZE if sanitize else [], "the catchment-sums host program")
-
-
-def run_cases(cases, sanitize=False):
-    """cases: dicts with series [T, N] (float32 or float64: the case's dtype), offsets [B + 1], and optionally order, weights
-    [N], status [N], rows_per_wave (1, or 4: the kernel's row groups of many-catchment jobs), and for the spread ids [N] + grad
-    [TG, B].  Returns per case (sums [T, B], weight_sums [B], spread
-    [TG, N] in the case's dtype or None)."""
-    exe = program(sanitize)
-    blob, shapes = [struct.pack("i", len(cases))], []
-    for c in cases:
-        series = np.asarray(c["series"])
-        dt = series.dtype
-        assert dt in (np.float32, np.float64)
-        T, N = series.shape
-        B = len(c["offsets"]) - 1
-        order, w, st, grad = c.get("order"), c.get("weights"), c.get("status"), c.get("grad")
-        TG = 0 if grad is None else np.asarray(grad).shape[0]
-        blob.append(struct.pack("9i", int(dt == np.float64), T, N, B, -1 if order is None else len(order), int(w is not None),
-                                int(st is not None), TG, int(c.get("rows_per_wave", 1))))
-        blob.append(np.ascontiguousarray(series).tobytes())
-        blob.append(np.asarray(c["offsets"], dtype=np.int32).tobytes())
-        if order is not None:
-            blob.append(np.asarray(order, dtype=np.int32).tobytes())
-        if w is not None:
-            assert np.asarray(w).dtype == dt
-            blob.append(np.ascontiguousarray(w).tobytes())
-        if st is not None:
-            blob.append(np.asarray(st, dtype=np.int32).tobytes())
-        if TG:
-            blob.append(np.asarray(c["ids"], dtype=np.int32).tobytes())
-            blob.append(np.ascontiguousarray(np.asarray(grad, dtype=np.float64)).tobytes())
-        shapes.append((dt, T, N, B, TG))
-    with tempfile.TemporaryDirectory() as tmp:
-        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
-        with open(fin, "wb") as fh:
-            fh.write(b"".join(blob))
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-        p = subprocess.run([exe, fin, fout], capture_output=True, text=True, env=env, timeout=300)
-        assert p.returncode == 0 and not p.stderr.strip(), (p.returncode, p.stderr[-4000:])
-        raw = open(fout, "rb").read()
-    res, at = [], 0
-
-    def take(dtype, *shape):
-        nonlocal at
-        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        a = np.frombuffer(raw[at:at + n], dtype=dtype).reshape(shape).copy()
-        at += n
-        return a
-
-    for dt, T, N, B, TG in shapes:
-        res.append((take(np.float64, T, B), take(np.float64, B), take(dt, TG, N) if TG else None))
-    assert at == len(raw)
-    return res
+def case(c):
+    """c: a dict with series [T, N] (float32 or float64: the case's dtype), offsets [B + 1], and optionally order, weights [N],
+    status [N], rows_per_wave (1, or 4: the kernel's row groups of many-catchment jobs), and for the spread ids [N] + grad
+    [TG, B].  The case of post_host.run that gives (sums [T, B], weight_sums [B], spread [TG, N] in the case's dtype or None)."""
+    series = np.asarray(c["series"])
+    dt = series.dtype
+    T, N = series.shape
+    B = len(c["offsets"]) - 1
+    i32 = lambda a: None if a is None else np.asarray(a, dtype=np.int32)
+    order, w, st, grad = i32(c.get("order")), c.get("weights"), i32(c.get("status")), c.get("grad")
+    assert w is None or np.asarray(w).dtype == dt
+    sums, wsum, spread = Out(np.float64, T, B), Out(np.float64, B), None
+    calls = [("catchment_sums", [dtype_code(dt), T, N, B, 0 if order is None else len(order), int(c.get("rows_per_wave", 1))],
+              [series, i32(c["offsets"]), order, w, st, sums, wsum])]
+    if grad is not None and len(grad):
+        grad = np.asarray(grad, dtype=np.float64)
+        spread = Out(dt, grad.shape[0], N)
+        calls.append(("catchment_spread", [dtype_code(dt), grad.shape[0], B, N], [grad, i32(c["ids"]), w, st, spread]))
+    return calls, (sums, wsum, spread)

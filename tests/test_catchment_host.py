@@ -1,14 +1,15 @@
 """CPU: the catchment sums (lgar_catchment_sums / lgar_catchment_spread, include/lgar.h).
 
 The per-lane accumulation and the combine order the GPU kernel runs (lgar_py_amd/csrc/lgar_catchment.hpp) are compiled for the
-host into a small stand-alone program (tests/catchment_host).  Its sums must equal the numpy statement of the definition
-(catchment_host.sums_ref: a plain loop over the 256 partials and the tree) BIT FOR BIT; the same program built with
+host into a small stand-alone program (tests/post_host).  Its sums must equal the numpy statement of the definition
+(post_host.catchment.sums_ref: a plain loop over the 256 partials and the tree) BIT FOR BIT; the same program built with
 AddressSanitizer + UBSan must also get through a corrupt map clean.  CatchmentMap's host logic (the stable sort, the
 contiguous fast path, -1, every rejection) needs no GPU either."""
 import numpy as np
 import pytest
 
-import catchment_host as CH
+import post_host as PH
+from post_host import catchment as CH
 
 T = 3
 N = sum(CH.SIZES)  # 2121
@@ -46,7 +47,7 @@ KEYS = [(dt, w, p, f) for dt in (np.float64, np.float32) for w in (False, True) 
 def results():
     """Every combination in ONE run of the host program; the numpy reference is computed once per case."""
     cases = [_case(*k) for k in KEYS]
-    got = CH.run_cases(cases)
+    got = PH.run(map(CH.case, cases))
     ref = [CH.sums_ref(c["series"], c["offsets"], c["order"], c.get("weights"), c.get("status")) for c in cases]
     return {k: (c, g, r) for k, c, g, r in zip(KEYS, cases, got, ref)}
 
@@ -78,7 +79,7 @@ def test_four_rows_per_wave_give_the_same_bits(dtype):
     """In jobs of many catchments a wave carries its catchment through four rows at once (column, status and weight read once
     for the four, one set of partials per row): six rows -- a full group and a ragged one -- against the same numpy loop."""
     cases = [dict(_case(dtype, w, p, True, seed=5, T=6), rows_per_wave=4) for w in (False, True) for p in (False, True)]
-    for c, (sums, wsum, _) in zip(cases, CH.run_cases(cases)):
+    for c, (sums, wsum, _) in zip(cases, PH.run(map(CH.case, cases))):
         rs, rw = CH.sums_ref(c["series"], c["offsets"], c["order"], c.get("weights"), c.get("status"))
         assert sums.shape == (6, len(CH.SIZES)) and CH.same_bits(sums, rs) and CH.same_bits(wsum, rw)
 
@@ -90,7 +91,7 @@ def test_catchments_beyond_one_block_of_loads(dtype):
     full group and a ragged one), weighted and flagged, contiguous and permuted, against the same numpy loop."""
     cases = [dict(_case(dtype, True, p, True, seed=9, T=5, sizes=CH.BIG_SIZES), rows_per_wave=r) for p in (False, True) for r in (1, 4)]
     cases.append(_case(dtype, False, False, False, seed=10, T=2, sizes=CH.BIG_SIZES))
-    for c, (sums, wsum, _) in zip(cases, CH.run_cases(cases)):
+    for c, (sums, wsum, _) in zip(cases, PH.run(map(CH.case, cases))):
         rs, rw = CH.sums_ref(c["series"], c["offsets"], c["order"], c.get("weights"), c.get("status"))
         assert sums.shape[1] == len(CH.BIG_SIZES) and CH.same_bits(sums, rs) and CH.same_bits(wsum, rw) and np.isfinite(sums).all()
     assert wsum.tolist() == list(CH.BIG_SIZES)  # (the last case: no weights, nothing flagged)
@@ -104,12 +105,12 @@ def test_flagged_members_are_skipped_not_multiplied_by_zero(results):
     other = dict(c, series=c["series"].copy())
     bad = (c["status"] & CH.FAULT_MASK) != 0
     other["series"][:, bad] = 12345.0
-    (s2, w2, _), = CH.run_cases([other])
+    (s2, w2, _), = PH.run(map(CH.case, [other]))
     assert CH.same_bits(sums, s2) and CH.same_bits(wsum, w2)
     # a status word without a fault bit does not skip: clearing it changes nothing, setting a fault bit there does
     kept = dict(c, status=np.where(c["status"] == 128, 0, c["status"]))
     dropped = dict(c, status=np.where(c["status"] == 128, 64, c["status"]))
-    (s3, *_), (s4, *_) = CH.run_cases([kept, dropped])
+    (s3, *_), (s4, *_) = PH.run(map(CH.case, [kept, dropped]))
     assert CH.same_bits(sums, s3) and not CH.same_bits(sums, s4)
 
 
@@ -120,7 +121,7 @@ def test_a_catchment_is_a_function_of_its_own_members():
     alone = dict(series=np.concatenate([np.full((T, 77), np.nan, np.float32), c["series"][:, lo:]], axis=1),
                  weights=np.concatenate([np.zeros(77, np.float32), c["weights"][lo:]]),
                  offsets=np.array([0, 77, 77 + 1000], dtype=np.int32))
-    (full, fw, _), (part, pw, _) = CH.run_cases([c, alone])
+    (full, fw, _), (part, pw, _) = PH.run(map(CH.case, [c, alone]))
     assert CH.same_bits(full[:, -1], part[:, 1]) and fw[-1] == pw[1] and np.isnan(part[:, 0]).all()
 
 
@@ -137,7 +138,7 @@ def test_spread_on_the_host(results, dtype):
     ids[5:9] = -1
     ids[100] = 40  # (beyond B: no catchment either)
     c = dict(_case(dtype, True, False, False), ids=ids)
-    (_, _, spread), = CH.run_cases([c])
+    (_, _, spread), = PH.run(map(CH.case, [c]))
     assert CH.same_bits(spread, CH.spread_ref(c["grad"], ids, c["weights"], None, dtype))
     assert (spread[:, 5:9] == 0).all() and (spread[:, 100] == 0).all() and (spread[:, 9:100] != 0).all()
 
@@ -169,8 +170,8 @@ def test_sanitizer_build_on_the_cases_and_a_corrupt_map():
         bad = _corrupt(dtype)
         cases += [bad, dict(bad, rows_per_wave=4), dict(_case(dtype, True, True, True, T=6), rows_per_wave=4), dict(bad, order=None, offsets=np.array([0, 90, 40, 130, -6, 280, 5000], dtype=np.int32)),
                   dict(bad, series=bad["series"][:, :0], weights=bad["weights"][:0], status=bad["status"][:0], ids=bad["ids"][:0])]
-    got = CH.run_cases(cases, sanitize=True)
-    plain = CH.run_cases(cases)
+    got = PH.run(map(CH.case, cases), sanitize=True)
+    plain = PH.run(map(CH.case, cases))
     for c, a, b in zip(cases, got, plain):
         for x, y in zip(a, b):
             assert (x is None and y is None) or CH.same_bits(x, y)

@@ -295,11 +295,166 @@ def test_entry_points_the_simulator_lacks_raise():
     from lgar_py_amd import LgarError
     pr, pe = _forcing()
     eng = _engine()
-    with pytest.raises(LgarError, match="simulator has no lgar_soil_moisture"):
-        eng.soil_moisture()
-    with pytest.raises(LgarError, match="simulator has no lgar_totals_replay"):
-        eng.run_with_soil_moisture(pr, pe, every=4)
+    with pytest.raises(LgarError, match="simulator has no basin sums of the soil moisture"):
+        eng.soil_moisture(basin=True)
+    with pytest.raises(LgarError, match="simulator has no basin sums of the soil moisture"):
+        eng.soil_moisture(weights=[1.0, 2.0, 3.0, 4.0], basin=torch.zeros(3, dtype=torch.float64))
     with pytest.raises(LgarError, match="simulator has no lgar_cooperating_lanes"):
         eng.cooperating_lanes()
     with pytest.raises(LgarError, match="with_state=False"):
         eng.like(*[getattr(eng, k) for k in PARAMS], with_state=False).forward(pr, pe)
+
+
+# ... and what it has: the post-processing entry points, from the host build of their headers (tests/post_host) -----------
+EDGES = [0.0, 10.0, 50.0, 1000.0]  # the last bin reaches below the column: it is divided by its in-column width
+F64_F32 = pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["fp64", "fp32"])
+
+
+def _profile(eng, edges, what):
+    """The numpy definition on the engine's own front table, rounded once to the engine's dtype."""
+    from post_host import moisture as MH
+    fr = eng.fronts()
+    ref = MH.profile_ref(fr["depth"], fr["theta"], fr["layer"], fr["n_fronts"], eng.thickness.numpy(), edges, what)
+    return ref.astype(fr["depth"].dtype)
+
+
+@F64_F32
+def test_soil_moisture_equals_the_numpy_definition_bit_for_bit(dtype):
+    from post_host import same_bits
+    pr, pe = _forcing()
+    eng = _engine(dtype=dtype)
+    eng.forward(pr, pe)
+    assert int(eng.n_fronts.max()) > eng.L and not bool(eng.status.any())
+    for edges in (None, EDGES):
+        for what in ("theta", "storage"):
+            got = eng.soil_moisture(edges, what)
+            assert got.dtype == dtype and tuple(got.shape) == (3, 4)
+            assert same_bits(got.numpy(), _profile(eng, edges, what)), (edges, what)
+    out = torch.empty(3, 4, dtype=dtype)
+    assert eng.soil_moisture(EDGES, "storage", out=out) is out and torch.equal(out, got)
+
+
+@F64_F32
+@pytest.mark.parametrize("rows", [12, 10], ids=["whole_windows", "ragged_tail"])
+def test_windows_with_snapshots_equal_one_forward(rows, dtype):
+    """(tests/test_gpu_moisture.py's window test at the smallest shape.)  every=4: every series, the state, the status and the
+    run totals are those of ONE forward() over the same rows; snapshot r is soil_moisture() of an engine stepped 4 (r + 1) rows."""
+    names = ("runoff", "infiltration", "AET", "ending_volume")
+    pr, pe = _forcing(rows=rows)
+    one, eng, step = _engine(dtype=dtype), _engine(dtype=dtype), _engine(dtype=dtype)
+    want = one.forward(pr, pe, series=names)
+    got = eng.run_with_soil_moisture(pr, pe, every=4, edges=EDGES, what="storage", series=names)
+    assert sorted(got) == sorted(names + ("soil_moisture",)) and all(torch.equal(got[nm], want[nm]) for nm in names)
+    assert float(want["infiltration"].sum()) > 0.0
+    a, b = _state(eng), _state(one)
+    assert _same(a[:8] + a[9:], b[:8] + b[9:]) and torch.equal(eng.totals[:8], one.totals[:8])
+    assert float(one.totals[:8].abs().sum()) > 0.0
+    assert tuple(got["soil_moisture"].shape) == (rows // 4, 3, 4)
+    for r in range(rows // 4):
+        step.forward(pr[4 * r:4 * r + 4], pe[4 * r:4 * r + 4])
+        assert torch.equal(got["soil_moisture"][r], step.soil_moisture(EDGES, "storage")), r
+
+
+def _catchment_job():
+    """Six columns of crash_insert_water_bench_col2 under rain scaled per column (the unscaled ones fault where the reference
+    crashes), spun up to three rows before that step; ids in a non-contiguous order with an empty catchment (1) and a column of
+    none; 12 rows."""
+    import devsim
+    g = _golden("crash_insert_water_bench_col2")
+    crash = int(g["crash_step"])
+    scale = np.array([[1.0, 0.95, 1.0, 0.9, 0.3, 0.95]])
+    f = g["forcing"]
+    pr, pe = f[:, 0:1] * scale, np.repeat(f[:, 1:2], 6, 1)
+    eng = _engine(6, "crash_insert_water_bench_col2")
+    eng.forward(pr[:crash - 3], pe[:crash - 3], series=())
+    assert not bool(eng.status.any())
+    cmap = devsim.SimCatchmentMap([2, 0, -1, 2, 0, 2], n_catchments=4, weights=[0.5, 2.0, 1.0, 0.25, 1.5, 0.125], device="cpu")
+    routing = devsim.SimCatchmentRouting(list(g["giuh_ordinates"]), device="cpu")
+    return eng, cmap, routing, pr[crash - 3:crash + 9], pe[crash - 3:crash + 9]
+
+
+def _check_catchment_block(res, eng, cmap, routing, queues):
+    """One forward()'s catchment sums, weight sums and routed sums against the numpy definitions; queues: {name: the queue the
+    call started from}, replaced by the queue it must have left."""
+    from post_host import catchment as CH, route as RH, same_bits
+    st = eng.status.numpy()
+    for nm in ("runoff", "giuh_runoff"):
+        sums, wsum = CH.sums_ref(res[nm].numpy(), cmap.offsets_host, cmap.order_host, cmap.weights_host.numpy(), st)
+        assert same_bits(res["catchment:" + nm].numpy(), sums) and same_bits(res["catchment:weight"].numpy(), wsum), nm
+        y, queues[nm] = RH.route_ref(sums, routing.ordinates_host.numpy(), queues.get(nm))
+        assert same_bits(res["catchment:routed:" + nm].numpy(), y) and same_bits(routing.queue_of(nm).numpy(), queues[nm]), nm
+    return wsum
+
+
+def test_catchment_sums_and_routing_through_forward_in_one_call_and_in_two():
+    """forward(catchments=, catchment=, routing=) on the simulator: the [T, B] sums equal sums_ref of the returned series with
+    the engine's status (the faulted column drops out of every row), the weight sums are those of the columns left, the routed
+    sums equal route_ref; 12 rows as 5 + 7 give the bits of one call, the queue carried across the cut included."""
+    names = ("runoff", "giuh_runoff")
+    eng, cmap, routing, pr, pe = _catchment_job()
+    assert cmap.order is not None and cmap.sizes.tolist() == [2, 0, 3, 0]
+    one = eng.forward(pr, pe, series=names, catchments=cmap, catchment=names, routing=routing)
+    st = eng.status.tolist()
+    assert st[0] != 0 and st[2] == st[0] and st[1] == st[3] == st[4] == st[5] == 0  # a member of catchment 2, and the column of none
+    queues = {}
+    wsum = _check_catchment_block(one, eng, cmap, routing, queues)
+    assert wsum.tolist() == [3.5, 0.0, 0.375, 0.0]
+    assert bool((one["catchment:runoff"][:5, [0, 2]] > 0).all()) and bool((one["catchment:runoff"][:, [1, 3]] == 0).all())
+    assert bool((one["catchment:routed:giuh_runoff"][:, [0, 2]] > 0).all())  # (the queues are still draining at the end)
+    # ... and cut after five rows: the fault (row 3) lies before the cut, so every row is summed over the same columns
+    eng2, cmap2, routing2, _, _ = _catchment_job()
+    queues2, parts = {}, []
+    for lo, hi in ((0, 5), (5, 12)):
+        parts.append(eng2.forward(pr[lo:hi], pe[lo:hi], series=names, catchments=cmap2, catchment=names, routing=routing2))
+        _check_catchment_block(parts[-1], eng2, cmap2, routing2, queues2)
+    for key in ("catchment:runoff", "catchment:giuh_runoff", "catchment:routed:runoff", "catchment:routed:giuh_runoff"):
+        assert torch.equal(torch.cat([p[key] for p in parts]), one[key]), key
+    assert all(torch.equal(routing2.queue_of(nm), routing.queue_of(nm)) for nm in names)
+    assert torch.equal(parts[-1]["catchment:weight"], one["catchment:weight"])
+
+
+@F64_F32
+@pytest.mark.parametrize("T", [0, 1, 6])
+def test_catchment_sum_under_autograd(T, dtype):
+    import devsim
+    from lgar_py_amd import catchment_sum
+    from post_host import catchment as CH, same_bits
+    rng = np.random.default_rng(T)
+    ids, w = [2, 0, -1, 2, 0, 2], rng.random(6)
+    status = torch.tensor([0, 0, 0, 4, 128, 0], dtype=torch.int32)
+    cmap = devsim.SimCatchmentMap(ids, n_catchments=3, weights=w, device="cpu")
+    series = torch.tensor(rng.standard_normal((T, 6)), dtype=dtype, requires_grad=True)
+    grad = torch.tensor(rng.standard_normal((T, 3)))
+    out = catchment_sum(series, cmap, status)
+    wd = cmap.weights(dtype).numpy()
+    assert same_bits(out.detach().numpy(), CH.sums_ref(series.detach().numpy(), cmap.offsets_host, cmap.order_host, wd, status.numpy())[0])
+    out.backward(grad)
+    assert series.grad.dtype == dtype
+    assert same_bits(series.grad.numpy(), CH.spread_ref(grad.numpy(), ids, wd, status.numpy(), series.detach().numpy().dtype))
+
+
+@pytest.mark.parametrize("per", [False, True], ids=["shared", "per_catchment"])
+@pytest.mark.parametrize("K", [1, 5])
+@pytest.mark.parametrize("T", [0, 1, 6])
+def test_catchment_route_under_autograd(T, K, per, monkeypatch):
+    """Through a routing object (its ordinates are constants) and through an ordinates tensor that takes a gradient."""
+    import devsim
+    from lgar_py_amd import catchment_route, catchments
+    from post_host import route as RH, same_bits
+    monkeypatch.setattr(catchments, "CatchmentRouting", devsim.SimCatchmentRouting)  # (what catchment_route builds for a tensor)
+    rng = np.random.default_rng(10 * T + K)
+    g = torch.tensor(rng.random((3, K) if per else K), requires_grad=True)
+    gk = g.detach().numpy().T if per else g.detach().numpy()  # the device layout: [K, B] or [K]
+    x = torch.tensor(rng.standard_normal((T, 3)), requires_grad=True)
+    gy, q_in = torch.tensor(rng.standard_normal((T, 3))), torch.tensor(rng.standard_normal((K, 3)))
+    y = catchment_route(x, g, queue=q_in)
+    assert same_bits(y.detach().numpy(), RH.route_ref(x.detach().numpy(), gk, q_in.numpy())[0])
+    y.backward(gy)
+    assert same_bits(x.grad.numpy(), RH.adjoint_ref(gy.numpy(), gk))
+    gg = torch.from_numpy(RH.ordinate_grad_ref(x.detach().numpy(), gy.numpy(), K))  # [K, B]
+    assert torch.equal(g.grad, gg.t().contiguous() if per else gg.sum(dim=1))
+    x2 = x.detach().clone().requires_grad_(True)
+    y2 = catchment_route(x2, devsim.SimCatchmentRouting(g.detach(), n_catchments=3, device="cpu"))
+    assert same_bits(y2.detach().numpy(), RH.route_ref(x.detach().numpy(), gk)[0])
+    y2.backward(gy)
+    assert torch.equal(x2.grad, x.grad)

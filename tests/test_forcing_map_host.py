@@ -221,8 +221,7 @@ def test_lgar_series_with_a_map_gives_the_gradients_of_the_gathered_forcing(monk
 # 7 ------------------------------------------------------------------------------------------------------------------------
 def test_the_engine_goes_on_after_a_mapped_call_whose_forcing_columns_do_not_divide_n():
     """B = 5 forcing columns over N = 70 columns, and over N = 72, which 5 does not divide: after that mapped forward the
-    engine's LgarDims carry a layout no unmapped call accepts.  reset() and a plain [T, N] forward equal a fresh engine's bit for bit (the
-    simulator has no lgar_soil_moisture: tests/test_gpu_forcing_map.py does this with it on the GPU), and the library's own
+    engine's LgarDims carry a layout no unmapped call accepts.  reset() and a plain [T, N] forward equal a fresh engine's bit for bit, and the library's own
     check of the dims an entry point that reads no forcing performs (lgar_cooperating_lanes: host logic) accepts them."""
     from lgar_py_amd import _capi
     idx = J.index(N)

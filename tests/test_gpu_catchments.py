@@ -12,7 +12,7 @@ import pytest
 from _golden import engine_keywords
 from conftest import GOLDEN
 
-import catchment_host as CH
+from post_host import catchment as CH
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")

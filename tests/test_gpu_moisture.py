@@ -12,7 +12,7 @@ import pytest
 from _golden import engine_keywords
 from conftest import GOLDEN
 
-import moisture_host as MH
+from post_host import moisture as MH
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")

@@ -15,7 +15,7 @@ import pytest
 from _golden import engine_keywords
 from conftest import GOLDEN
 
-import route_host as RH
+from post_host import route as RH
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")

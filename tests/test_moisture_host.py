@@ -1,8 +1,8 @@
 """CPU: the soil-moisture output (lgar_soil_moisture, include/lgar.h) on the REFERENCE's own front tables.
 
 The per-column function the GPU kernel runs (lgar_py_amd/csrc/lgar_moisture.hpp) is compiled for the host into a small
-stand-alone program (tests/moisture_host) and run over the front table the reference recorded at every step of every
-trajectory fixture.  Its results must equal the numpy statement of the definition (moisture_host.profile_ref) bit for bit, and
+stand-alone program (tests/post_host) and run over the front table the reference recorded at every step of every
+trajectory fixture.  Its results must equal the numpy statement of the definition (post_host.moisture.profile_ref) bit for bit, and
 the definition itself must close the reference's mass balance: the storage bins that cover the column sum to the recorded
 ending_volume (Layer.mass_balance, layers/Layer.py:795-824)."""
 import numpy as np
@@ -10,7 +10,8 @@ import pytest
 
 from conftest import golden_names
 
-import moisture_host as MH
+import post_host as PH
+from post_host import moisture as MH
 
 TRAJ = [n for n in golden_names() if not n.startswith("grad_")]
 NONMONOTONE = {"manyfronts_pulse_84": (2, 4, 6), "bushland_hourly_1500": (1405,)}  # steps with a front above its predecessor
@@ -34,7 +35,7 @@ def results():
                 for what in ("theta", "storage"):
                     cases.append(dict(t, edges=edges, what=what))
                     keys.append((name, dtype, edges is None, what))
-    got = MH.run_cases(cases)
+    got = PH.run(map(MH.case, cases))
     ref = [MH.profile_ref(c["depth"], c["theta"], c["layer"], c["n_fronts"], c["thickness"], c["edges"], c["what"]) for c in cases]
     return {k: (c, a, r) for k, c, a, r in zip(keys, cases, got, ref)}
 
@@ -83,14 +84,14 @@ def test_bins_below_the_column():
     t = MH.tables("synth1_phil")
     Z = t["Z"]  # 200 cm
     edges = [0.0, 44.0, Z - 10.0, Z + 10.0, Z + 20.0, Z + 30.0]
-    th, st = MH.run_cases([dict(t, edges=edges, what="theta"), dict(t, edges=edges, what="storage")])
+    th, st = PH.run(map(MH.case, [dict(t, edges=edges, what="theta"), dict(t, edges=edges, what="storage")]))
     assert np.isnan(th[3:]).all() and (st[3:] == 0.0).all() and np.isfinite(th[:3]).all()
     # the straddling bin holds the bottom layer's last 10 cm: its mean theta is that front's theta, not half of it
     last = t["theta"][t["n_fronts"] - 1, np.arange(len(t["n_fronts"]))]
     assert np.abs(th[2] - last).max() <= 1e-14 and np.abs(st[2] - 10.0 * last).max() <= 1e-13
     assert MH.same_bits(th, MH.profile_ref(t["depth"], t["theta"], t["layer"], t["n_fronts"], t["thickness"], edges, "theta"))
     # layer mode never has a bin below the column
-    lay, = MH.run_cases([dict(t, edges=None, what="theta")])
+    lay, = PH.run(map(MH.case, [dict(t, edges=None, what="theta")]))
     assert np.isfinite(lay).all()
 
 
@@ -100,7 +101,7 @@ def test_more_bins_than_the_smallest_kernel_capacity():
     for nb in (9, 16, 17, 32):
         edges = np.linspace(0.0, t["Z"] + 7.0, nb + 1)
         for what in ("theta", "storage"):
-            got, = MH.run_cases([dict(t, edges=edges, what=what)])
+            got, = PH.run(map(MH.case, [dict(t, edges=edges, what=what)]))
             assert MH.same_bits(got, MH.profile_ref(t["depth"], t["theta"], t["layer"], t["n_fronts"], t["thickness"], edges, what))
 
 
@@ -119,8 +120,31 @@ def test_sanitizer_build_on_fixtures_and_a_corrupt_state():
     bad["n_fronts"][1] = -7
     cases += [dict(bad, edges=[0.0, 10.0, 300.0], what="theta"), dict(bad, edges=None, what="storage"),
               dict({k: (v.astype(np.float32) if v.dtype == np.float64 else v) for k, v in bad.items()}, edges=None, what="theta")]
-    got = MH.run_cases(cases, sanitize=True)
-    plain = MH.run_cases(cases)
+    got = PH.run(map(MH.case, cases), sanitize=True)
+    plain = PH.run(map(MH.case, cases))
     for a, b in zip(got, plain):
         assert MH.same_bits(a, b)
     assert (got[-2][:, 1] == 0.0).all()  # n_fronts < 0 clamps to an empty table
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["fp64", "fp32"])
+def test_totals_replay_adds_row_after_row_in_the_series_dtype(dtype):
+    """lgar_totals_replay's host launcher, plain and under AddressSanitizer + UBSan: running[j] gains the rows of series[j] one
+    after the other, in the series' own dtype, from what it held; an absent series leaves its row alone, row 7 is never touched,
+    and two chunks through the carried block equal one call over all rows."""
+    rng = np.random.default_rng(2)
+    N, T = 5, 7
+    series = [None if j == 2 else ((rng.random((T, N)) - 0.3) * 10.0 ** rng.integers(-3, 4, (T, N))).astype(dtype) for j in range(7)]
+    start = rng.random((8, N)).astype(dtype)
+    want = start.copy()
+    for j, s in enumerate(series):
+        for t in range(T if s is not None else 0):
+            want[j] = want[j] + s[t]
+    call = lambda rows, running: ([("totals_replay", [PH.dtype_code(dtype), N, rows.stop - rows.start],
+                                    [None if s is None else s[rows] for s in series] + [running])], running)
+    for sanitize in (False, True):
+        whole = PH.Out(dtype, 8, N, start=start)
+        got, first = PH.run([call(slice(0, T), whole), call(slice(0, 3), PH.Out(dtype, 8, N, start=start))], sanitize=sanitize)
+        second, = PH.run([call(slice(3, T), PH.Out(dtype, 8, N, start=first))], sanitize=sanitize)
+        assert MH.same_bits(got, want) and MH.same_bits(second, want) and not MH.same_bits(first, want)
+        assert MH.same_bits(got[[2, 7]], start[[2, 7]])

@@ -1,9 +1,9 @@
 """CPU: catchment routing (lgar_catchment_route / lgar_catchment_route_grad, include/lgar.h).
 
 The fold without a dependence between rows, the queue hand-over and the ordinate-gradient accumulation the GPU kernels run
-(lgar_py_amd/csrc/lgar_route.hpp) are compiled for the host into a small stand-alone program (tests/route_host).  It is held
+(lgar_py_amd/csrc/lgar_route.hpp) are compiled for the host into a small stand-alone program (tests/post_host).  It is held
 BIT FOR BIT to the reference's own recorded giuh_runoff and giuh_runoff_queue (every committed fixture with num_subcycles = 1)
-and to the numpy statement of the definition (route_host.route_ref: the queue recurrence itself); the same program built with
+and to the numpy statement of the definition (post_host.route.route_ref: the queue recurrence itself); the same program built with
 AddressSanitizer + UBSan runs the same cases.  CatchmentRouting's host logic needs no GPU either."""
 import os
 
@@ -13,7 +13,8 @@ import pytest
 from _golden import steps_before_crash
 from conftest import GOLDEN, golden_names
 
-import route_host as RH
+import post_host as PH
+from post_host import route as RH
 
 RUNOFF, GIUH_RUNOFF = 4, 6  # ACC_NAMES
 
@@ -42,7 +43,7 @@ def fixtures():
 def test_reference_parity_bit_for_bit(fixtures):
     """Routing the reference's own runoff column with the fixture's ordinates gives the reference's giuh_runoff column and its
     queue after the last row, bit for bit (all fixtures in ONE run of the host program, each a B = 1 case)."""
-    got = RH.run_cases([dict(mode="forward", x=x[:, None], g=g) for _, x, _, _, g in fixtures])
+    got = PH.run(map(RH.case, [dict(mode="forward", x=x[:, None], g=g) for _, x, _, _, g in fixtures]))
     for (nm, x, want, queue, g), (y, q_out) in zip(fixtures, got):
         assert RH.same_bits(y[:, 0], want), nm
         assert RH.same_bits(q_out[:, 0], queue[-1]), nm
@@ -61,7 +62,7 @@ def test_resume_at_a_cut_from_the_reference_queue(fixtures):
                 cases.append(dict(mode="forward", x=x[:cut, None], g=g))
                 cases.append(dict(mode="forward", x=x[cut:, None], g=g, q_in=queue[cut - 1][:, None]))
                 index.append((nm, cut, want, queue))
-    got = RH.run_cases(cases)
+    got = PH.run(map(RH.case, cases))
     assert len(index) >= 3 * 50
     for i, (nm, cut, want, queue) in enumerate(index):
         (y0, q0), (y1, q1) = got[2 * i], got[2 * i + 1]
@@ -106,7 +107,7 @@ def _check(cases, refs, got):
 def test_host_build_equals_the_numpy_definition_bit_for_bit(definition_cases):
     """The fold of the kernels against the recurrence of the definition: mixed signs, a NaN and -0.0 in the inputs."""
     cases, refs = definition_cases
-    _check(cases, refs, RH.run_cases(cases))
+    _check(cases, refs, PH.run(map(RH.case, cases)))
     # T = 0 hands the queue over as it is; without one it is +0.0
     for c, (y, q) in zip(cases, refs):
         if c["mode"] == "forward" and c["x"].shape[0] == 0:
@@ -134,10 +135,10 @@ def test_chunked_routing_equals_one_call(definition_cases):
     for K in (5, 8):
         for per in (False, True):
             x, _, g, q_in = RH.mixed_data(rng, 11, 65, K, per)
-            (whole, q_whole), = RH.run_cases([dict(mode="forward", x=x, g=g, q_in=q_in)])
+            (whole, q_whole), = PH.run(map(RH.case, [dict(mode="forward", x=x, g=g, q_in=q_in)]))
             q, at, parts = q_in, 0, []
             for n in (3, 1, 7):
-                (y, q), = RH.run_cases([dict(mode="forward", x=x[at:at + n], g=g, q_in=q)])
+                (y, q), = PH.run(map(RH.case, [dict(mode="forward", x=x[at:at + n], g=g, q_in=q)]))
                 parts.append(y)
                 at += n
             assert RH.same_bits(np.concatenate(parts), whole) and RH.same_bits(q, q_whole)
@@ -149,7 +150,7 @@ def test_sanitizer_build_on_the_same_cases(definition_cases, fixtures):
     references.  Any finding aborts the program."""
     cases, refs = definition_cases
     extra = [dict(mode="forward", x=x[:, None], g=g) for _, x, _, _, g in fixtures[:3]]
-    got = RH.run_cases(cases + extra, sanitize=True)
+    got = PH.run(map(RH.case, cases + extra), sanitize=True)
     _check(cases, refs, got[:len(cases)])
     for (nm, x, want, queue, g), (y, q_out) in zip(fixtures[:3], got[len(cases):]):
         assert RH.same_bits(y[:, 0], want) and RH.same_bits(q_out[:, 0], queue[-1]), nm
