@@ -341,6 +341,51 @@ int32_t lgar_catchment_route(const double *x, int32_t n_rows, int32_t n_catchmen
 int32_t lgar_catchment_route_grad(const double *x, const double *gy, int32_t n_rows, int32_t n_catchments,
                                   int32_t n_ordinates, double *g_out, void *stream);
 
+/* Catchment scores: per-catchment moments of a simulation against observations with gaps, and their adjoint (what a catchment
+ * job compares with observations: every metric -- MSE, NSE, KGE, bias, correlation -- is a few operations on these [B] vectors).
+ *
+ * All arrays are fp64, catchment fastest: sim[T][B] the model rows (the output of the routing above, say), obs[To][B] the
+ * observations, window = r >= 1 and T == To * r (r model rows under one observation row: 5-minute steps, hourly gauges).
+ * A pair (j, b) is VALID iff obs[j][b] is finite: NaN, +inf and -inf all mark a gap.  Nothing about sim decides validity; a
+ * NaN in sim on a valid row poisons that catchment's moments, as it should.  The aggregated simulation is
+ *     s[j][b] = (((0.0 + sim[j r][b]) + sim[j r + 1][b]) + ... + sim[j r + r - 1][b]) / (double)r
+ * THE GATED FOLD of a term x[j][b] over j: the rows are cut into blocks of LGAR_SCORE_BLOCK = 64 observation rows, block k =
+ * rows 64 k .. min(64 k + 63, To - 1); a block partial starts at +0.0 and adds the terms of its valid rows in increasing j
+ * (an invalid row adds NOTHING: not 0 * NaN, no term at all); the result starts at +0.0 and adds the block partials in
+ * increasing k.  Plain fp64 adds and products (-ffp-contract=off).  The block size is a constant of the definition, not of the
+ * launch, so the result for catchment b is a pure function of column b of the inputs -- not of B, the launch shape or the run.
+ *
+ * moments[LGAR_SCORE_NMOM = 7][B], WRITTEN, not added to:
+ *     row 0  n   = the number of valid rows (exact, as a double)
+ *     row 1  mo  = fold(o) / n
+ *     row 2  ms  = fold(s) / n                      (IEEE divides: n = 0 gives NaN for both means)
+ *     row 3  soo = fold((o - mo) * (o - mo))
+ *     row 4  sss = fold((s - ms) * (s - ms))
+ *     row 5  sos = fold((o - mo) * (s - ms))
+ *     row 6  see = fold((s - o) * (s - o))
+ * With no valid row, rows 3 .. 6 are +0.0.  To = 0 gives n = 0; B = 0 is a no-op.
+ *
+ * workspace: device scratch of lgar_catchment_moments_workspace(To, B) bytes, owned by the caller (the library allocates
+ * nothing): it holds the block partials between the launches of a call and nothing between calls.  That function returns
+ * LGAR_E_ARG for a negative size.
+ * Negative sizes, window < 1, To * window beyond int32, a null pointer the sizes say will be read or written, or a null
+ * workspace where the workspace function returns more than 0, return LGAR_E_ARG. */
+#define LGAR_SCORE_BLOCK 64
+#define LGAR_SCORE_NMOM 7
+int64_t lgar_catchment_moments_workspace(int32_t n_obs_rows, int32_t n_catchments);
+int32_t lgar_catchment_moments(const double *sim, const double *obs, int32_t n_obs_rows, int32_t n_catchments, int32_t window,
+                               double *moments, void *workspace, void *stream);
+
+/* The adjoint of the moments.  Every differentiable function F of them has, on the valid rows,
+ *     dF / ds[j][b] = c0 / n + 2 c1 (s - ms) + c2 (o - mo) + 2 c3 (s - o),      c = dF / d(ms, sss, sos, see)
+ * and 0 elsewhere (n, mo and soo do not depend on sim; the terms through the means cancel: the centred sums are stationary in
+ * them).  coef[4][B] holds c, moments the result of lgar_catchment_moments on the same sim and obs.  s is recomputed and
+ *     g = ((c0[b] / n[b] + (2.0 * c1[b]) * (s - ms)) + c2[b] * (o - mo)) + (2.0 * c3[b]) * (s - o)
+ * evaluated in exactly that order; grad_sim[j r + i][b] = g / (double)r for i < r, and +0.0 on every row of an invalid j.
+ * Elementwise: no reduction, nothing to zero; grad_sim[T][B] is written. */
+int32_t lgar_catchment_moments_grad(const double *sim, const double *obs, int32_t n_obs_rows, int32_t n_catchments,
+                                    int32_t window, const double *moments, const double *coef, double *grad_sim, void *stream);
+
 /* Run totals of a run cut into several lgar_forward calls.  lgar_forward sums a call's accumulators step by step from zero
  * and adds that sum to LgarState.totals, so a chunked run adds several partial sums where one call adds one: the same numbers in
  * another order, equal to the last bits only.  This replays the one-call order over series the chunks stored: for every j < 7
