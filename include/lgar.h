@@ -386,6 +386,58 @@ int32_t lgar_catchment_moments(const double *sim, const double *obs, int32_t n_o
 int32_t lgar_catchment_moments_grad(const double *sim, const double *obs, int32_t n_obs_rows, int32_t n_catchments,
                                     int32_t window, const double *moments, const double *coef, double *grad_sim, void *stream);
 
+/* Catchment network: linear Muskingum channel routing BETWEEN catchments.  A gauge at an outlet sees the catchment's own routed
+ * runoff plus everything that arrives from the catchments upstream, delayed and attenuated by the channels; this is the stage
+ * between lgar_catchment_route and lgar_catchment_moments.  One reach is the channel of one catchment.
+ *
+ * All floating-point arrays are fp64, catchment fastest: the lateral inflow x[T][B], the discharge y[T][B], the coefficients
+ * coef[3][B] = c0, c1, c2 of every reach.  x and y do not overlap.
+ * TOPOLOGY, int32.  On the device:
+ *     down[B]                 the catchment b drains into, -1 for an outlet.  A forest: at most one downstream each, no cycles.
+ *     up_ptr[B + 1], up_idx[E] CSR lists of the direct upstream catchments of every b, IN ASCENDING INDEX within a list;
+ *                             E = n_edges = B minus the number of outlets.
+ *     order[B]                the catchments sorted by (level, index); level(b) = 0 without upstream, else 1 + max level(u).
+ * In HOST memory:
+ *     level_ptr[n_levels + 1] delimits the levels inside order.  The library never reads DEVICE memory on the host; level_ptr
+ *                             is host memory and the library reads it, on the host, to launch one kernel per level.
+ *
+ * FORWARD.  For every reach b, with Iprev, Oprev = state_in[0][b], state_in[1][b] (state_in == NULL: +0.0), for t = 0 .. T - 1:
+ *     I = x[t][b];  for e = up_ptr[b] .. up_ptr[b + 1] - 1:  I = I + y[t][up_idx[e]]      (ascending e, one rounded add each)
+ *     O = (c0[b] * I + c1[b] * Iprev) + c2[b] * Oprev                                    (exactly this association; -ffp-contract=off)
+ *     y[t][b] = O;  Iprev = I;  Oprev = O
+ * state_out[0][b], state_out[1][b] = Iprev, Oprev after row T - 1 (state_out == NULL: not wanted).  y and state_out are
+ * WRITTEN, not added to; the caller zeroes nothing.  T = 0 copies the state (zeros when state_in is NULL); B = 0 is a no-op.
+ * The result for b is a pure function of the columns of x and coef in its upstream closure -- not of B, of the other
+ * catchments, of the launch or of the run.  coef = (1, 0, 0) is plain upstream accumulation, (0, 1, 0) a one-row lag per reach.
+ * Muskingum with storage constant K and weight X: c0 = (dt/2 - K X) / D, c1 = (dt/2 + K X) / D, c2 = (K - K X - dt/2) / D,
+ * D = K - K X + dt/2; the kernels take coefficients and do not restrict their sign.
+ *
+ * The levels run in ascending order, one launch each on `stream`; stream order is the only dependence between them.
+ * Every index the kernels read from device memory is clamped into its array (order, up_idx, down to [0, B - 1]; up_ptr to
+ * [0, n_edges]): a corrupt topology gives wrong numbers, never an access out of bounds.  Offsets are 64-bit.
+ * Negative sizes, n_levels < 0, a level_ptr that does not start at 0, end at B and never decrease, or a null pointer the sizes
+ * say will be read or written, return LGAR_E_ARG. */
+int32_t lgar_network_route(const double *x, int32_t n_rows, int32_t n_catchments, const double *coef, const int32_t *up_ptr,
+                           const int32_t *up_idx, int32_t n_edges, const int32_t *order, const int32_t *level_ptr, int32_t n_levels,
+                           const double *state_in, double *state_out, double *y, void *stream);
+
+/* The adjoint of the network routing with respect to x and, when gc != NULL, the gradient with respect to coef.  The levels run
+ * in DESCENDING order, so gx[.][down[b]] is complete before b runs.  For each reach lam_next = +0.0 and, with gc wanted, three
+ * accumulators gc0, gc1, gc2 = +0.0; for t = T - 1 .. 0:
+ *     a = gy[t][b];  if down[b] >= 0:  a = a + gx[t][down[b]]
+ *     lam = a + c2[b] * lam_next
+ *     gx[t][b] = c0[b] * lam + c1[b] * lam_next
+ *     gc0 = gc0 + lam * I[t];   gc1 = gc1 + lam * I[t - 1];   gc2 = gc2 + lam * y[t - 1][b]          (only when gc is wanted)
+ *     lam_next = lam
+ * I[t] is re-formed from x and the stored y (the result of lgar_network_route on the same x, coef, state_in) by the forward's own
+ * fold, so it has the same bits; I[-1], y[-1] come from state_in, or are zeros.  The carried state is a constant: nothing flows
+ * back into it.  gx[T][B] and gc[3][B] are WRITTEN.  gy and gx do not overlap.  gc == NULL: x, y, up_ptr, up_idx, state_in are
+ * not read.  The refusals of lgar_network_route, and gc wanted without x, y, up_ptr, up_idx, return LGAR_E_ARG. */
+int32_t lgar_network_route_grad(const double *gy, int32_t n_rows, int32_t n_catchments, const double *coef, const int32_t *down,
+                                const int32_t *order, const int32_t *level_ptr, int32_t n_levels, double *gx, const double *x,
+                                const double *y, const int32_t *up_ptr, const int32_t *up_idx, int32_t n_edges,
+                                const double *state_in, double *gc, void *stream);
+
 /* Run totals of a run cut into several lgar_forward calls.  lgar_forward sums a call's accumulators step by step from zero
  * and adds that sum to LgarState.totals, so a chunked run adds several partial sums where one call adds one: the same numbers in
  * another order, equal to the last bits only.  This replays the one-call order over series the chunks stored: for every j < 7
