@@ -438,6 +438,67 @@ int32_t lgar_network_route_grad(const double *gy, int32_t n_rows, int32_t n_catc
                                 const double *y, const int32_t *up_ptr, const int32_t *up_idx, int32_t n_edges,
                                 const double *state_in, double *gc, void *stream);
 
+/* Catchment baseflow: a groundwater store per catchment, fed by the catchment sums of percolation, that returns water to the
+ * channel through the exponential storage-discharge relation (the nonlinear reservoir coupled below this infiltration scheme in
+ * NextGen / CFE).  Its result is added to the routed runoff ahead of lgar_network_route.
+ *
+ * All arrays are fp64, catchment fastest: the recharge r[T][B], the baseflow q[T][B], the storage s[T][B], the parameters
+ * par[3][B] = cgw, expon, smax.  r, s, smax and the state share one depth unit (cm per row, or area-weighted cm); cgw is in that
+ * unit per hour; dt_h is the row step in hours.
+ *
+ * FORWARD.  For every catchment b, with S = state_in[b] (state_in == NULL: +0.0), for t = 0 .. T - 1:
+ *     A  = S + r[t][b]
+ *     z  = expon[b] * (A / smax[b])
+ *     zc = z < 0 ? 0 : (z > LGAR_GW_ZMAX ? LGAR_GW_ZMAX : z)                 (selects: a NaN stays a NaN)
+ *     e  = gw_exp(zc)
+ *     f  = (cgw[b] * dt_h) * (e - 1.0)
+ *     qq = f > A ? A : f                                                    (the store cannot give more than it holds)
+ *     qq = qq < 0 ? 0 : qq
+ *     S  = A - qq
+ *     q[t][b] = qq;   s[t][b] = S                                           (s == NULL: not wanted)
+ * in exactly this association, without contraction (-ffp-contract=off).  state_out[b] = S after the last row (NULL: not wanted).
+ * q, s and state_out are WRITTEN, not added to.  T = 0 copies the state (zeros when state_in is NULL); B = 0 is a no-op.  Mass
+ * closes per catchment up to rounding: state_in + sum r = sum q + state_out.  The result for b is a pure function of column b
+ * of r and par and of state_in[b]: a NaN in r[t][b] reaches q and s of catchment b from row t on and no other catchment.
+ * Ties go where the selects send them: f == A is flux (qq = f), z == 0 and z == LGAR_GW_ZMAX are not clamped, qq == 0 is not
+ * "clamped to 0".
+ *
+ * gw_exp(zc), 0 <= zc <= LGAR_GW_ZMAX, uses no libm, no fma and no hardware reciprocal -- numpy restates it one operation for one:
+ *     k = rint(zc * LOG2E)                  computed as (zc * LOG2E + 1.5 * 2^52) - 1.5 * 2^52 (two rounded adds, ties to even)
+ *     r = (zc - k * LN2_HI) - k * LN2_LO    LN2_HI = 0x1.62e42fee00000p-1 (32 trailing zero bits: k * LN2_HI is exact for
+ *                                           k <= 58), LN2_LO = 0x1.a39ef35793c76p-33, LOG2E = 0x1.71547652b82fep+0
+ *     p = sum_{j <= 13} r^j / j!            Horner from j = 13 down: p = p * r + c_j, one rounded multiply and one rounded add per
+ *                                           step, c_j the correctly rounded 1 / j!
+ *     e = ldexp(p, k)                       exact
+ *
+ * Negative sizes, a null pointer the sizes say will be read or written (T > 0: r, par, q), or a dt_h that is not finite or
+ * <= 0, return LGAR_E_ARG.  Parameter VALUES are not policed: smax = 0 gives the IEEE result.  One launch on `stream`; offsets
+ * are 64-bit. */
+#define LGAR_GW_ZMAX 40.0
+int32_t lgar_catchment_baseflow(const double *r, int32_t n_rows, int32_t n_catchments, const double *par, double dt_h,
+                                const double *state_in, double *state_out, double *q, double *s, void *stream);
+
+/* The adjoint of the baseflow store: from gq[T][B] and gs[T][B] (gs == NULL: zeros), the incoming gradients of q and s, the
+ * gradients with respect to r (gr[T][B]), to the parameters (gpar[3][B] = gcgw, gexpon, gsmax; NULL: not wanted) and to the
+ * initial storage (gstate[B]; NULL: not wanted).  s is the storage the forward stored for the same r, par, dt_h, state_in.  A of
+ * row t is re-formed as s[t - 1][b] + r[t][b] (row 0: state_in[b], or +0.0), and z, zc, e, f and the regime of the row come from
+ * the forward's own function: the same bits.  With lam = +0.0 and three accumulators from +0.0, for t = T - 1 .. 0:
+ *     lam = lam + gs[t][b];   w = gq[t][b] - lam;   ce = (cgw[b] * dt_h) * e
+ *     zero    ((f > A ? A : f) < 0: qq was clamped to 0):   dA = 0;  no parameter terms
+ *     emptied (not zero, f > A: qq = A >= 0):               dA = 1;  no parameter terms
+ *     flux    (neither), z < 0 or z > LGAR_GW_ZMAX:         dA = 0;  gcgw = gcgw + w * (dt_h * (e - 1.0))
+ *     flux, 0 <= z <= LGAR_GW_ZMAX:                         dA = ce * (expon[b] / smax[b]);
+ *                                                           gcgw   = gcgw   + w * (dt_h * (e - 1.0))
+ *                                                           gexpon = gexpon + w * (ce * (A / smax[b]))
+ *                                                           gsmax  = gsmax  + w * (-(ce * zc) / smax[b])
+ *     gr[t][b] = lam + w * dA;   lam = gr[t][b]
+ * gstate[b] = lam after row 0.  gr, gpar and gstate are WRITTEN; every accumulator receives its terms in decreasing t, and an
+ * accumulator that receives no term in a row keeps its bits.  T = 0 writes zeros.  The refusals of lgar_catchment_baseflow
+ * (T > 0: gq, r, s, par, gr), and so gpar or gstate wanted without s, return LGAR_E_ARG. */
+int32_t lgar_catchment_baseflow_grad(const double *gq, const double *gs, const double *r, const double *s, int32_t n_rows,
+                                     int32_t n_catchments, const double *par, double dt_h, const double *state_in, double *gr,
+                                     double *gpar, double *gstate, void *stream);
+
 /* Run totals of a run cut into several lgar_forward calls.  lgar_forward sums a call's accumulators step by step from zero
  * and adds that sum to LgarState.totals, so a chunked run adds several partial sums where one call adds one: the same numbers in
  * another order, equal to the last bits only.  This replays the one-call order over series the chunks stored: for every j < 7

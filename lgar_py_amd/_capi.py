@@ -18,6 +18,7 @@ NTICKETS = 8
 MOIST_BINS = 32  # LGAR_MOIST_BINS
 ROUTE_KMAX = 64  # LGAR_ROUTE_KMAX
 SCORE_BLOCK, SCORE_NMOM = 64, 7  # LGAR_SCORE_BLOCK, LGAR_SCORE_NMOM
+GW_ZMAX = 40.0  # LGAR_GW_ZMAX
 MOIST_WHAT = {"theta": 0, "storage": 1}  # lgar_soil_moisture's `what`
 ST_RESUME, ST_FAULT_MASK = 128, 0x7F
 NSCAL = 3 + GMAX
@@ -31,7 +32,7 @@ STATUS_NAMES = {1: "NaN", 2: "negative pow base", 4: "theta order", 8: "front ov
 ABI_VERSION = 4  # LGAR_ABI_VERSION of include/lgar.h this binding mirrors
 EXPORTS = ["lgar_version", "lgar_abi_version", "lgar_sizeof_dims", "lgar_fmax", "lgar_lmax", "lgar_cooperating_lanes", "lgar_state_init", "lgar_forward", "lgar_forward_tangent",
            "lgar_soil_moisture", "lgar_totals_replay", "lgar_catchment_sums", "lgar_catchment_spread", "lgar_catchment_route", "lgar_catchment_route_grad",
-           "lgar_catchment_moments_workspace", "lgar_catchment_moments", "lgar_catchment_moments_grad", "lgar_network_route", "lgar_network_route_grad", "lgar_leaf_batch", "lgar_valu_probe", "lgar_valu_probe_insts"]
+           "lgar_catchment_moments_workspace", "lgar_catchment_moments", "lgar_catchment_moments_grad", "lgar_network_route", "lgar_network_route_grad", "lgar_catchment_baseflow", "lgar_catchment_baseflow_grad", "lgar_leaf_batch", "lgar_valu_probe", "lgar_valu_probe_insts"]
 
 
 class LgarDims(C.Structure):
@@ -158,6 +159,11 @@ def load():
         lib.lgar_network_route.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]
         lib.lgar_network_route_grad.restype = i32
         lib.lgar_network_route_grad.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    if hasattr(lib, "lgar_catchment_baseflow") or not os.environ.get("LGAR_LIB"):
+        lib.lgar_catchment_baseflow.restype = i32
+        lib.lgar_catchment_baseflow.argtypes = [vp, i32, i32, vp, dbl, vp, vp, vp, vp, vp]
+        lib.lgar_catchment_baseflow_grad.restype = i32
+        lib.lgar_catchment_baseflow_grad.argtypes = [vp, vp, vp, vp, i32, i32, vp, dbl, vp, vp, vp, vp, vp]
     lib.lgar_leaf_batch.restype = i32
     lib.lgar_leaf_batch.argtypes = [i32, i32, vp, vp, dbl, vp, vp, vp, vp, vp, i32, dbl, vp, i32, vp]
     lib.lgar_valu_probe_insts.restype = i32
