@@ -236,6 +236,41 @@ int32_t lgar_forward_tangent(const LgarDims *dims, const LgarParams *params, con
                              void *grad_out, void *tangent_runoff, int32_t *status, int32_t dtype, void *stream,
                              uint32_t *tickets);
 
+/* The resumable tangent: lgar_forward_tangent over a WINDOW of rows that may start from a carried state and hand its end
+ * state back.  A state is a value state plus its tangent parts (the derivative of every stored value along `direction`).
+ *  - Carry: a run cut into chunks -- state_out / dstate_out / grad_out of one call given as state_in / dstate_in / grad_in of
+ *    the next -- leaves the bits of one call over all rows (grad_out, tangent_runoff, both end states).
+ *  - Stop-gradient: the value state of a spun-up run (what lgar_forward left) with dstate_in = NULL gives the exact derivative,
+ *    with respect to the parameters, of "lgar_forward from this fixed state over these rows".  Nothing flows into the spin-up.
+ *  - state_in = NULL is lgar_forward_tangent itself, bit for bit.  A fresh start is NOT a zero tangent state: the fresh state
+ *    depends on the parameters (theta(initial_psi; alpha, n), the deepest front's K).
+ * Forcing layouts, column_map, forcing_group, tangent_share, tickets, dtype and layer counts are lgar_forward_tangent's.  With
+ * tangent_share = W the caller guarantees in addition that the W columns of a group hold the same VALUE state.
+ * grad_out[c] is grad_in[c] followed by this call's terms in row order (grad_out may be grad_in).  status is written, not read:
+ * a column whose state_in has fewer fronts than layers gets LGAR_ST_STRUCT; n_fronts is clamped on load as in lgar_forward.
+ * state_in / dstate_in are never written: a column handed over in the front-capacity chain is redone from them (a state that
+ * arrives with more fronts than the first kernel holds is handed over before its first row), and only the kernel that finishes
+ * a column writes its grad_out and end state.  state_out is written as lgar_forward's store writes it -- rows [0, n_fronts) of
+ * the per-front arrays, n_fronts, scalars; totals and tickets are not touched -- so lgar_forward and lgar_soil_moisture accept
+ * it.  n_steps = 0 copies state, tangent state and grad through.
+ * LGAR_E_ARG: everything lgar_forward_tangent refuses; a null window; dstate_in without state_in; exactly one of state_out /
+ * dstate_out; a given state with a null array among those read or written; an output state that shares an array with an input
+ * state or with the other output state (the pointers are compared). */
+typedef struct {
+  const LgarState *state_in;    /* NULL: fresh state (set_internal_states), exactly lgar_forward_tangent's start */
+  const LgarState *dstate_in;   /* tangent parts of state_in; NULL: zeros.  Read: depth, theta, psi, k, dzdt
+                                   [front_slots][n_columns], scalars [LGAR_NSCAL][n_columns].  flags, n_fronts, totals,
+                                   tickets are ignored.  Must be NULL when state_in is NULL. */
+  LgarState *state_out;         /* NULL: not wanted.  Value state after the last row: a state lgar_forward accepts. */
+  LgarState *dstate_out;        /* its tangent parts; given iff state_out is given */
+  const void *grad_in;          /* [n_columns] (dtype) or NULL = zeros: the fold of grad continues from it */
+} LgarTangentWindow;
+
+int32_t lgar_forward_tangent_window(const LgarDims *dims, const LgarParams *params, const LgarParams *direction,
+                                    const LgarForcing *forcing, const void *w_runoff, const void *w_perc,
+                                    const LgarTangentWindow *window, void *grad_out, void *tangent_runoff, int32_t *status,
+                                    int32_t dtype, void *stream, uint32_t *tickets);
+
 /* Soil-moisture output: the water the front table holds in depth bins (the product the reference reserves and never fills:
  * GlobalParams.soil_moisture_wetting_fronts, physics/GlobalParams.py:61; LGAR-C's soil_moisture_layers).  The theta profile
  * implied by a front table is piecewise constant: front j (depth d_j, water content theta_j, layer tag k_j) reaches up to

@@ -30,7 +30,7 @@ ST_NAN, ST_NEGBASE, ST_THETA_ORDER, ST_OVERFLOW, ST_ITERCAP, ST_BOTTOM, ST_STRUC
 STATUS_NAMES = {1: "NaN", 2: "negative pow base", 4: "theta order", 8: "front overflow", 16: "iteration cap",
                 32: "front reached domain bottom", 64: "structural error"}
 ABI_VERSION = 4  # LGAR_ABI_VERSION of include/lgar.h this binding mirrors
-EXPORTS = ["lgar_version", "lgar_abi_version", "lgar_sizeof_dims", "lgar_fmax", "lgar_lmax", "lgar_cooperating_lanes", "lgar_state_init", "lgar_forward", "lgar_forward_tangent",
+EXPORTS = ["lgar_version", "lgar_abi_version", "lgar_sizeof_dims", "lgar_fmax", "lgar_lmax", "lgar_cooperating_lanes", "lgar_state_init", "lgar_forward", "lgar_forward_tangent", "lgar_forward_tangent_window",
            "lgar_soil_moisture", "lgar_totals_replay", "lgar_catchment_sums", "lgar_catchment_spread", "lgar_catchment_route", "lgar_catchment_route_grad",
            "lgar_catchment_moments_workspace", "lgar_catchment_moments", "lgar_catchment_moments_grad", "lgar_network_route", "lgar_network_route_grad", "lgar_catchment_baseflow", "lgar_catchment_baseflow_grad", "lgar_leaf_batch", "lgar_valu_probe", "lgar_valu_probe_insts"]
 
@@ -57,6 +57,11 @@ class LgarState(C.Structure):
 class LgarForcing(C.Structure):
     # (LgarForcing(precip, pet) leaves column_map NULL: no map)
     _fields_ = [("precip", C.c_void_p), ("pet", C.c_void_p), ("column_map", C.c_void_p)]
+
+
+class LgarTangentWindow(C.Structure):
+    # pointers to LgarState structs (the caller keeps them alive across the call), and the [N] gradient the fold continues from
+    _fields_ = [(nm, C.c_void_p) for nm in ("state_in", "dstate_in", "state_out", "dstate_out", "grad_in")]
 
 
 class LgarStepOut(C.Structure):
@@ -132,6 +137,10 @@ def load():
         lib.lgar_forward_tangent.restype = i32
         lib.lgar_forward_tangent.argtypes = [p(LgarDims), p(LgarParams), p(LgarParams), p(LgarForcing), vp, vp, vp, vp, vp,
                                              i32, vp, vp]
+    if hasattr(lib, "lgar_forward_tangent_window") or not os.environ.get("LGAR_LIB"):  # (a library selected by hand may predate it)
+        lib.lgar_forward_tangent_window.restype = i32
+        lib.lgar_forward_tangent_window.argtypes = [p(LgarDims), p(LgarParams), p(LgarParams), p(LgarForcing), vp, vp,
+                                                    p(LgarTangentWindow), vp, vp, vp, i32, vp, vp]
     if hasattr(lib, "lgar_soil_moisture") or not os.environ.get("LGAR_LIB"):  # (a measurement variant built before it existed)
         lib.lgar_soil_moisture.restype = i32
         lib.lgar_soil_moisture.argtypes = [p(LgarDims), p(LgarParams), p(LgarState), vp, i32, i32, vp, vp, vp, i32, vp]

@@ -26,14 +26,18 @@ BATCH_DIRECTIONS_MAX_COLUMNS = 1 << 23
 SHARE_MIN_LANES = 65536  # columns x directions: one wave on every SIMD of the chip
 
 
-def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcing_map=None):
+def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcing_map=None, start=None):
     """Vector-Jacobian product for every (kind, layer) in `wanted` (list of (kind, l)).
     Returns ({(kind, l): grad[N]}, tangent_status[N]).  Columns are independent, so the directions are laid side by side as
     len(wanted) * N columns of a single launch (fills the chip even for ensembles of 10^5 columns; very large jobs go in
     groups of directions).  A column whose tangent integration faults (status != 0: NaN, iteration cap, front overflow
     ...) has no valid gradient: with check=True that raises LgarStatusError (a ValueError, like the reference's physics
     faults), with check=False its gradient entries are zeroed and the status tensor says which columns those are.
-    forcing_map: a forcing.ForcingMap with one entry per column -- precip / pet are [T, B], the weights stay [T, N]."""
+    forcing_map: a forcing.ForcingMap with one entry per column -- precip / pet are [T, B], the weights stay [T, N].
+    start: None = the run starts from a fresh state; an engine.EngineState (LgarEngine.snapshot()) = the rows are a window that
+    starts from that FIXED state (LgarEngine.tangent_window: the derivative of forward() from the state, nothing flows into the
+    run that produced it).  Where the directions ride side by side the state is laid out with them (repeat_interleave: (5 F +
+    NSCAL) * Dg * N values, small beside the [T, N] arrays)."""
     L, N, D = eng.L, eng.N, len(wanted)
     out = {}
     status = torch.zeros(N, dtype=torch.int32, device=eng.device)
@@ -54,7 +58,11 @@ def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcin
             kind, l = part[0]
             dmat = torch.zeros(L, N, dtype=eng.dtype, device=eng.device)
             dmat[l] = 1.0
-            out[(kind, l)], _, st = eng.tangent({kind: dmat}, precip, pet, w_runoff=w_runoff, w_perc=w_perc, forcing_map=forcing_map)
+            if start is None:
+                out[(kind, l)], _, st = eng.tangent({kind: dmat}, precip, pet, w_runoff=w_runoff, w_perc=w_perc, forcing_map=forcing_map)
+            else:
+                out[(kind, l)], _, st, _ = eng.tangent_window({kind: dmat}, precip, pet, w_runoff=w_runoff, w_perc=w_perc,
+                                                              forcing_map=forcing_map, start=start, keep_state=False)
             status |= st
             continue
         # column n's Dg directions sit in ADJACENT lanes (column n * Dg + b): they follow the same branches, so a wavefront
@@ -65,11 +73,13 @@ def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcin
         dirs = {k: torch.zeros(L, Dg * N, dtype=eng.dtype, device=eng.device) for k in KINDS}
         for b, (kind, l) in enumerate(part):
             dirs[kind][l, b::Dg] = 1.0
-        g, _, st = big.tangent(dirs, precip, pet, w_runoff=w_runoff, w_perc=w_perc, forcing_group=Dg,  # forcing / weights broadcast by the kernel
-                               share=Dg if share else 0,
-                               # the SAME map, not replicated: entry c // Dg of the launch is the original column, and the
-                               # incoming [T, N] gradient is the [T, Dg * N // Dg] weight array as it is
-                               forcing_map=forcing_map)
+        # forcing / weights broadcast by the kernel (forcing_group); the SAME map, not replicated: entry c // Dg of the launch is
+        # the original column, and the incoming [T, N] gradient is the [T, Dg * N // Dg] weight array as it is
+        kw = dict(w_runoff=w_runoff, w_perc=w_perc, forcing_group=Dg, share=Dg if share else 0, forcing_map=forcing_map)
+        if start is None:
+            g, _, st = big.tangent(dirs, precip, pet, **kw)
+        else:
+            g, _, st, _ = big.tangent_window(dirs, precip, pet, start=start.expand(Dg), keep_state=False, **kw)
         for b, key in enumerate(part):
             out[key] = g[b::Dg].contiguous()
             status |= st[b::Dg]
@@ -86,7 +96,8 @@ def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcin
 
 
 class LgarSeriesFunction(torch.autograd.Function):
-    """(alpha, n, ksat)[L, N] -> (runoff, percolation)[T, N] from a fresh state; differentiable in alpha/n/ksat."""
+    """(alpha, n, ksat)[L, N] -> (runoff, percolation)[T, N] from a fresh state, or from a given one held fixed; differentiable
+    in alpha/n/ksat."""
 
     @staticmethod
     def forward(ctx, alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, engine_kw):
@@ -94,6 +105,8 @@ class LgarSeriesFunction(torch.autograd.Function):
         check = engine_kw.pop("check", True)
         status_out = engine_kw.pop("status_out", None)
         fmap = engine_kw.pop("forcing_map", None)
+        start = engine_kw.pop("initial_state", None)
+        state_out = engine_kw.pop("state_out", None)
         eng = LgarEngine(alpha.detach(), n.detach(), ksat.detach(), theta_e, theta_r, thickness, **engine_kw)
         precip, pet = torch.as_tensor(precip), torch.as_tensor(pet)
         if fmap is not None:
@@ -106,12 +119,17 @@ class LgarSeriesFunction(torch.autograd.Function):
                                 % (eng.N, tuple(precip.shape), tuple(pet.shape)))
             rep = eng.N // int(precip.shape[1])
             precip, pet = precip.repeat(1, rep).contiguous(), pet.repeat(1, rep).contiguous()  # column c reads c % Nf
+        if start is not None:
+            eng.restore(start)  # (in place of the fresh state the constructor left)
         out = eng.forward(precip, pet, series=("runoff", "percolation"), check=check, forcing_map=fmap)
+        if state_out is not None:
+            state_out.append(eng.snapshot())
         if status_out is not None:
             status_out.append(eng.status)
         ctx.engine = eng
         ctx.forcing = (precip, pet)
         ctx.forcing_map = fmap
+        ctx.start = start
         ctx.in_dtypes = (alpha.dtype, n.dtype, ksat.dtype)
         ctx.check = check
         ctx.status_out = status_out
@@ -127,7 +145,7 @@ class LgarSeriesFunction(torch.autograd.Function):
         keep = (~fwd_bad).to(g_runoff.dtype)[None, :] if g_runoff is not None else None
         gr = None if g_runoff is None else g_runoff * keep
         gp = None if g_perc is None else g_perc * ((~fwd_bad).to(g_perc.dtype)[None, :])
-        vj, st = parameter_vjp(eng, precip, pet, gr, gp, wanted, check=False, forcing_map=ctx.forcing_map)
+        vj, st = parameter_vjp(eng, precip, pet, gr, gp, wanted, check=False, forcing_map=ctx.forcing_map, start=ctx.start)
         st = torch.where(fwd_bad, torch.zeros_like(st), st)
         if ctx.status_out is not None:
             ctx.status_out.append(st)  # [forward status, tangent status]
@@ -149,7 +167,13 @@ def lgar_series(alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, **engi
     engine_kw: LgarEngine keywords, plus check=False to keep going when columns fault: pass status_out=[] to receive the
     forward status tensor (appended by the forward pass) and the tangent status tensor (appended by the backward pass);
     faulted columns get zero gradient.  forcing_map=<forcing.ForcingMap>: the forcing is [T, B] and column c reads forcing column
-    forcing_map.index[c], in the forward run and in the backward pass alike: no [T, N] forcing exists anywhere."""
+    forcing_map.index[c], in the forward run and in the backward pass alike: no [T, N] forcing exists anywhere.
+    initial_state=<engine.EngineState> (LgarEngine.snapshot() of a spun-up engine over the same columns): the run starts from that
+    state instead of a fresh one, and the state is a CONSTANT: the gradient is the derivative, with respect to the parameters, of
+    the run from the fixed state over these rows.  Nothing flows into the spin-up that produced the state, although that spin-up
+    depended on the same parameters -- the usual "warm-up excluded from the gradient".  The backward pass integrates the tangent
+    over these rows only.  state_out=[]: the forward pass appends the end state (an EngineState), which the next window takes as
+    its initial_state.  initial_state=None is a run from a fresh state."""
     return LgarSeriesFunction.apply(alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, engine_kw)
 
 

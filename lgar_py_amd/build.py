@@ -14,7 +14,9 @@ LAYERS = (2, 3, 4, 5, 6)  # LGAR_LAYERS (csrc/lgar_plan.hpp): one translation un
 UNITS = [("lgar_kernels.hip", [], ""), ("lgar_probe.hip", [], ""), ("lgar_moisture.hip", [], ""), ("lgar_catchment.hip", [], ""),
          ("lgar_route.hip", [], ""), ("lgar_score.hip", [], ""), ("lgar_network.hip", [], ""), ("lgar_baseflow.hip", [], "")] + \
         [("lgar_kernels_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS] + \
-        [("lgar_tangent_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS]
+        [("lgar_tangent_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS] + \
+        [("lgar_tangent_window_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS]
+TANGENT_SOURCES = ("lgar_tangent_nl.hip", "lgar_tangent_window_nl.hip")  # what a build without the tangent leaves out
 SOURCES = sorted(set(u[0] for u in UNITS))
 # every header the units may include (taken from the directory: a header left off a hand-kept list would let a stale library
 # be reused after it changed)
@@ -130,7 +132,7 @@ def build_variant(name, extra_flags, verbose=False, layers=(3,), tangent=False):
     out = os.path.join(vdir, "liblgar_hip_%s.so" % name)
     units = [u for u in UNITS if not u[2] or int(u[2][1:]) in layers]
     if not tangent:
-        units = [u for u in units if u[0] != "lgar_tangent_nl.hip"]
+        units = [u for u in units if u[0] not in TANGENT_SOURCES]
     # -DLGAR_MEASURE: the measurement points of the device code take their definitions from csrc/lgar_measure.hpp
     flags = list(extra_flags) + ["-DLGAR_MEASURE", "-DLGAR_LAYERS(X)=" + " ".join("X(%d)" % n for n in layers)] + \
             ([] if tangent else ["-DLGAR_NO_TANGENT"])
@@ -150,7 +152,7 @@ def build_variant(name, extra_flags, verbose=False, layers=(3,), tangent=False):
 
 def build(force=False, verbose=False):
     """Compile csrc/*.hip -> csrc/liblgar_hip.so.  hipcc cross-compiles gfx950 without a GPU.  The translation units
-    (C-ABI, probe, and one per soil-layer count for the forward and the tangent kernels) are compiled concurrently into
+    (C-ABI, probe, and one per soil-layer count for the forward, the tangent and the tangent-window kernels) are compiled concurrently into
     csrc/obj/<fingerprint>/ and then linked.  Safe to call from several processes at once (file lock; the library is renamed
     into place)."""
     if not force and not _stale():

@@ -228,17 +228,25 @@ int32_t lgar_forward(const LgarDims *dims, const LgarParams *params, LgarState *
 int32_t lgar_forward_tangent(const LgarDims *dims, const LgarParams *params, const LgarParams *direction,
                              const LgarForcing *forcing, const void *w_runoff, const void *w_perc, void *grad_out,
                              void *tangent_runoff, int32_t *status, int32_t dtype, void *stream, uint32_t *tickets) {
-  int rc = check_dims(dims);
-  if (rc) return rc;
-  if (!params || !direction || !forcing || !grad_out || !status) return LGAR_E_ARG;
-  if (!params->alpha || !params->n || !params->ksat || !params->theta_e || !params->theta_r || !params->thickness)
-    return LGAR_E_ARG;
-  if (dims->n_steps > 0 && (!forcing->precip || !forcing->pet)) return LGAR_E_ARG;
-  rc = check_forcing_layout(dims, forcing);
+  const int rc = check_tangent_call(dims, params, direction, forcing, grad_out, status);
   if (rc) return rc;
   return by_layers(dims->n_layers, [&](auto nl) {
     return launch_tangent_nl<decltype(nl)::value>(dims, params, direction, forcing, w_runoff, w_perc, grad_out, tangent_runoff,
                                                   status, dtype, (hipStream_t)stream, tickets);
+  });
+}
+
+int32_t lgar_forward_tangent_window(const LgarDims *dims, const LgarParams *params, const LgarParams *direction,
+                                    const LgarForcing *forcing, const void *w_runoff, const void *w_perc,
+                                    const LgarTangentWindow *window, void *grad_out, void *tangent_runoff, int32_t *status,
+                                    int32_t dtype, void *stream, uint32_t *tickets) {
+  int rc = check_tangent_call(dims, params, direction, forcing, grad_out, status);
+  if (rc) return rc;
+  rc = check_window(window);
+  if (rc) return rc;
+  return by_layers(dims->n_layers, [&](auto nl) {
+    return launch_tangent_window_nl<decltype(nl)::value>(dims, params, direction, forcing, w_runoff, w_perc, window, grad_out,
+                                                         tangent_runoff, status, dtype, (hipStream_t)stream, tickets);
   });
 }
 #endif

@@ -74,6 +74,38 @@ inline int check_forcing_layout(const LgarDims *d, const LgarForcing *f) {
   return 0;
 }
 
+// What lgar_forward_tangent and lgar_forward_tangent_window refuse alike.
+inline int check_tangent_call(const LgarDims *d, const LgarParams *p, const LgarParams *dir, const LgarForcing *f, const void *grad_out,
+                              const int32_t *status) {
+  const int rc = check_dims(d);
+  if (rc) return rc;
+  if (!p || !dir || !f || !grad_out || !status) return LGAR_E_ARG;
+  if (!p->alpha || !p->n || !p->ksat || !p->theta_e || !p->theta_r || !p->thickness) return LGAR_E_ARG;
+  if (d->n_steps > 0 && (!f->precip || !f->pet)) return LGAR_E_ARG;
+  return check_forcing_layout(d, f);
+}
+
+// What lgar_forward_tangent_window refuses beyond that (include/lgar.h).
+inline int check_window(const LgarTangentWindow *w) {
+  if (!w) return LGAR_E_ARG;
+  if (w->dstate_in && !w->state_in) return LGAR_E_ARG;
+  if ((w->state_out != nullptr) != (w->dstate_out != nullptr)) return LGAR_E_ARG;
+  auto values = [](const LgarState *s) { return s->depth && s->theta && s->psi && s->k && s->dzdt && s->scalars; };
+  auto table = [](const LgarState *s) { return s->flags && s->n_fronts; };
+  if (w->state_in && !(values(w->state_in) && table(w->state_in))) return LGAR_E_ARG;
+  if (w->dstate_in && !values(w->dstate_in)) return LGAR_E_ARG;
+  if (w->state_out && !(values(w->state_out) && table(w->state_out) && values(w->dstate_out))) return LGAR_E_ARG;
+  // an output state over an input's arrays: a handed-over column is redone from the input, which must still be there
+  auto shares = [](const LgarState *o, const LgarState *i) {
+    return o && i && (o->depth == i->depth || o->theta == i->theta || o->psi == i->psi || o->k == i->k || o->dzdt == i->dzdt ||
+                      o->scalars == i->scalars || (o->flags && o->flags == i->flags) || (o->n_fronts && o->n_fronts == i->n_fronts));
+  };
+  if (shares(w->state_out, w->state_in) || shares(w->state_out, w->dstate_in) || shares(w->dstate_out, w->state_in) ||
+      shares(w->dstate_out, w->dstate_in) || shares(w->dstate_out, w->state_out))
+    return LGAR_E_ARG;
+  return 0;
+}
+
 // The forward / init kernels' argument block of one call: one kernel on its own, no work counter, one lane per column (the
 // launchers set ticket and coop; chain_step the position in a chain).
 template <typename R>

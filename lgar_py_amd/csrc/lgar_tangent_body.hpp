@@ -9,6 +9,11 @@
 // Front capacity: values + tangents double the LDS per front, so the first kernel runs with LGAR_CAP_SMALL slots; a
 // column that could outgrow them is flagged LGAR_ST_RESUME and the second kernel (LGAR_FMAX slots) integrates exactly
 // those columns again from their fresh state (a tangent run always starts from set_internal_states).
+//
+// Window kernels (lgar_forward_tangent_window, lgar_tangent_window_nl.hip): tangent_lane<..., WINDOW = true> starts from a value
+// state + tangent state (TWindow::in / din) instead of the fresh one, continues the fold of grad from grad_in, and the kernel
+// that FINISHES a column stores both states (TWindow::out / dout).  A handed-over column is redone from in / din / grad_in, which
+// nobody writes.  Everything about the window sits behind `if constexpr (WINDOW)`: the plain instantiations are what they were.
 #pragma once
 #include "lgar_dual.hpp"
 #include "lgar_plan.hpp"
@@ -33,6 +38,35 @@ template <typename R> struct TArgs {
   Glob<R> G;
   const int32_t *fmap;                                    // null, or [N / Fg] (LgarForcing.column_map), as KArgs::fmap; last
 };
+
+// One per-front state as the window kernels see it: LgarState's arrays that carry a value (in, out) or a tangent (din, dout:
+// flags and nf unused).  [F][N] / [N] / [LGAR_NSCAL][N], column fastest: a lane reads and writes its own column, coalesced.
+template <typename Q, typename B, typename I> struct TStateP {
+  Q *depth, *theta, *psi, *k, *dzdt;
+  B *flags;
+  I *nf;
+  Q *scalars;
+};
+// the window block of one lgar_forward_tangent_window call; it follows TArgs in the window kernels' argument block
+template <typename R> struct TWindow {
+  TStateP<const R, const uint8_t, const int32_t> in, din;  // in.depth null: fresh state; din.depth null: zero tangents
+  TStateP<R, uint8_t, int32_t> out, dout;                  // out.depth null: not wanted
+  const R *grad_in;                                        // [N] or null = zeros
+};
+template <typename R> struct TWArgs {
+  TArgs<R> a;
+  TWindow<R> w;
+};
+
+template <typename Q, typename B, typename I> inline TStateP<Q, B, I> make_tstate(const LgarState *s) {
+  TStateP<Q, B, I> t;
+  t.depth = s ? (Q *)s->depth : nullptr; t.theta = s ? (Q *)s->theta : nullptr; t.psi = s ? (Q *)s->psi : nullptr;
+  t.k = s ? (Q *)s->k : nullptr; t.dzdt = s ? (Q *)s->dzdt : nullptr;
+  t.flags = s ? (B *)s->flags : nullptr;
+  t.nf = s ? (I *)s->n_fronts : nullptr;
+  t.scalars = s ? (Q *)s->scalars : nullptr;
+  return t;
+}
 
 // the argument block of one lgar_forward_tangent call: one kernel on its own, no work counter (as make_args, lgar_plan.hpp)
 template <typename R>
@@ -64,9 +98,23 @@ inline TArgs<R> make_targs(const LgarDims *d, const LgarParams *p, const LgarPar
   return a;
 }
 
-template <typename R, int NL, int FMAX, int MODE>
+// ... and of one lgar_forward_tangent_window call
+template <typename R>
+inline TWArgs<R> make_twargs(const LgarDims *d, const LgarParams *p, const LgarParams *dir, const LgarForcing *f, const void *w_runoff,
+                             const void *w_perc, const LgarTangentWindow *win, void *grad_out, void *tangent_runoff, int32_t *status) {
+  TWArgs<R> t;
+  t.a = make_targs<R>(d, p, dir, f, w_runoff, w_perc, grad_out, tangent_runoff, status);
+  t.w.in = make_tstate<const R, const uint8_t, const int32_t>(win->state_in);
+  t.w.din = make_tstate<const R, const uint8_t, const int32_t>(win->dstate_in);
+  t.w.out = make_tstate<R, uint8_t, int32_t>(win->state_out);
+  t.w.dout = make_tstate<R, uint8_t, int32_t>(win->dstate_out);
+  t.w.grad_in = (const R *)win->grad_in;
+  return t;
+}
+
+template <typename R, int NL, int FMAX, int MODE, bool WINDOW = false>
 __device__ __forceinline__ void tangent_lane(const LGAR_KARG TArgs<R> *ap, size_t c, int lane, WaveLDS<Dual<R>, FMAX, 1> &lds,
-                                             R *xchg = nullptr) {
+                                             R *xchg = nullptr, const LGAR_KARG TWindow<R> *wp = nullptr) {
   using S = Dual<R>;
   const LGAR_KARG TArgs<R> &a = *ap;
   const size_t N = (size_t)a.N;
@@ -94,9 +142,47 @@ __device__ __forceinline__ void tangent_lane(const LGAR_KARG TArgs<R> *ap, size_
   col.share_lanes = (xchg != nullptr) ? a.share : 0;
   col.xchg = xchg;
   col.cap = FMAX < a.F ? FMAX : a.F;
-  col.init_state();
   R grad = R(0);
   bool handed_over = false;
+  if constexpr (WINDOW) {
+    const LGAR_KARG TWindow<R> &w = *wp;
+    if (w.in.depth != nullptr) {
+      // state HBM -> LDS / registers, as forward_lane loads it (n_fronts clamped), each value with its tangent
+      const bool dz = w.din.depth != nullptr;
+      const int nf_stored = w.in.nf[c];
+      const int nf = nf_stored < 0 ? 0 : (nf_stored > col.cap ? col.cap : nf_stored);
+      col.nf = nf;
+      col.status = (nf < NL) ? LGAR_ST_STRUCT : 0;  // not a state lgar_state_init / lgar_forward produced: column is skipped
+      col.new_front_frozen = false;
+      for (int i = 0; i < nf; i++) {
+        const size_t o = (size_t)i * N + c;
+        col.F.Z(i) = S(w.in.depth[o], dz ? w.din.depth[o] : R(0));
+        col.F.TH(i) = S(w.in.theta[o], dz ? w.din.theta[o] : R(0));
+        col.F.PS(i) = S(w.in.psi[o], dz ? w.din.psi[o] : R(0));
+        col.F.DZ(i) = S(w.in.dzdt[o], dz ? w.din.dzdt[o] : R(0));
+        col.F.flag(i) = w.in.flags[o];
+      }
+      col.ponded_water = S(w.in.scalars[0 * N + c], dz ? w.din.scalars[0 * N + c] : R(0));
+      col.previous_precip = S(w.in.scalars[1 * N + c], dz ? w.din.scalars[1 * N + c] : R(0));
+      col.ending_volume = S(w.in.scalars[2 * N + c], dz ? w.din.scalars[2 * N + c] : R(0));
+#pragma unroll
+      for (int i = 0; i < LGAR_GMAX; i++) col.giuh_q[i] = S(w.in.scalars[(3 + i) * N + c], dz ? w.din.scalars[(3 + i) * N + c] : R(0));
+      col.k_deepest = S(R(0));
+      if (nf > 0) col.k_deepest = S(w.in.k[(size_t)(nf - 1) * N + c], dz ? w.din.k[(size_t)(nf - 1) * N + c] : R(0));
+      col.drain();
+      if (nf_stored > col.cap) {
+        // more fronts than this kernel can hold: the next kernel of the chain takes the column before its first row, or
+        // (last kernel: more than the state arrays have rows) front overflow
+        if (!a.chain_last) handed_over = true;
+        else col.status |= LGAR_ST_OVERFLOW;
+      }
+    } else {
+      col.init_state();
+    }
+    if (w.grad_in != nullptr) grad = w.grad_in[c];
+  } else {
+    col.init_state();
+  }
   const size_t Nf = (size_t)a.Nf;
   // this column's forcing column: by the layout, or by the caller's index (read here, once, and clamped), as in forward_lane
   size_t cf;
@@ -121,6 +207,9 @@ __device__ __forceinline__ void tangent_lane(const LGAR_KARG TArgs<R> *ap, size_
     if (a.w_perc) wp_ahead = a.w_perc[ow];
   }
   for (int t = 0; t < a.T; t++) {
+    if constexpr (WINDOW) {
+      if (handed_over) break;  // (handed over at load)
+    }
     if (!a.chain_last && col.nf + a.G.nsub > FMAX) {
       handed_over = true;  // could outgrow this kernel's front capacity: the next kernel redoes this column
       break;
@@ -143,7 +232,38 @@ __device__ __forceinline__ void tangent_lane(const LGAR_KARG TArgs<R> *ap, size_
     if (a.tangent_runoff) a.tangent_runoff[(size_t)t * N + c] = col.a_runoff.d;
     col.drain();
   }
-  a.grad_out[c] = handed_over ? R(0) : grad;
+  if constexpr (WINDOW) {
+    // only the kernel that finishes a column writes its results: grad_out may be grad_in, and the next kernel reads that
+    if (!handed_over) {
+      a.grad_out[c] = grad;
+      const LGAR_KARG TWindow<R> &w = *wp;
+      if (w.out.depth != nullptr) {
+        // state LDS / registers -> HBM, as store_state writes it (rows [0, nf)), each value with its tangent
+        const int rows = col.nf < a.F ? col.nf : a.F;
+        for (int i = 0; i < rows; i++) {
+          const size_t o = (size_t)i * N + c;
+          const S kk = (i < col.nf - 1) ? col.front_k(i, pick(col.P, col.F.layer(i))) : col.k_deepest;
+          w.out.depth[o] = col.F.Z(i).v; w.dout.depth[o] = col.F.Z(i).d;
+          w.out.theta[o] = col.F.TH(i).v; w.dout.theta[o] = col.F.TH(i).d;
+          w.out.psi[o] = col.F.PS(i).v; w.dout.psi[o] = col.F.PS(i).d;
+          w.out.k[o] = kk.v; w.dout.k[o] = kk.d;
+          w.out.dzdt[o] = col.F.DZ(i).v; w.dout.dzdt[o] = col.F.DZ(i).d;
+          w.out.flags[o] = col.F.flag(i);
+        }
+        w.out.nf[c] = col.nf;
+        w.out.scalars[0 * N + c] = col.ponded_water.v; w.dout.scalars[0 * N + c] = col.ponded_water.d;
+        w.out.scalars[1 * N + c] = col.previous_precip.v; w.dout.scalars[1 * N + c] = col.previous_precip.d;
+        w.out.scalars[2 * N + c] = col.ending_volume.v; w.dout.scalars[2 * N + c] = col.ending_volume.d;
+#pragma unroll
+        for (int i = 0; i < LGAR_GMAX; i++) {
+          w.out.scalars[(3 + i) * N + c] = col.giuh_q[i].v;
+          w.dout.scalars[(3 + i) * N + c] = col.giuh_q[i].d;
+        }
+      }
+    }
+  } else {
+    a.grad_out[c] = handed_over ? R(0) : grad;
+  }
   a.status[c] = handed_over ? (col.status | LGAR_ST_RESUME) : col.status;
   if (a.pending_out != nullptr) {
     const unsigned long long m = any_lane(handed_over);

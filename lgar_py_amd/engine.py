@@ -32,6 +32,44 @@ class LgarStatusError(ValueError):
     """Physics fault in one or more columns (the reference raises ValueError / IndexError / AttributeError)."""
 
 
+_VALUE_FIELDS = ("depth", "theta", "psi", "k", "dzdt", "scalars")  # what carries a tangent as well
+
+
+class EngineState:
+    """The column state of an LgarEngine at one moment (LgarEngine.snapshot()): clones of depth, theta, psi, k, dzdt, flags
+    [front_slots, N], n_fronts [N], scalars [NSCAL, N] and status [N].  The run totals are bookkeeping of a run, not state."""
+    FIELDS = _VALUE_FIELDS[:5] + ("flags", "n_fronts", "scalars", "status")
+
+    def __init__(self, **tensors):
+        for nm in self.FIELDS:
+            setattr(self, nm, tensors[nm])
+
+    N = property(lambda self: self.depth.shape[1])
+    front_slots = property(lambda self: self.depth.shape[0])
+    dtype = property(lambda self: self.depth.dtype)
+    device = property(lambda self: self.depth.device)
+
+    def expand(self, times):
+        """Every column `times` times over, side by side (column c becomes columns c * times .. c * times + times - 1)."""
+        return EngineState(**{nm: getattr(self, nm).repeat_interleave(times, dim=-1) for nm in self.FIELDS})
+
+    def _struct(self):
+        return _capi.LgarState(*[getattr(self, nm).data_ptr() for nm in self.FIELDS[:8]], None, None)
+
+
+class TangentState:
+    """What LgarEngine.tangent_window hands from one window to the next: the value state (an EngineState), the tangent of every
+    value in it along the window's direction ({depth, theta, psi, k, dzdt: [front_slots, N], scalars: [NSCAL, N]}) and the
+    gradient folded so far ([N])."""
+
+    def __init__(self, value, tangent, grad):
+        self.value, self.tangent, self.grad = value, tangent, grad
+
+    def _struct(self):
+        t = self.tangent
+        return _capi.LgarState(*[t[nm].data_ptr() for nm in _VALUE_FIELDS[:5]], None, None, t["scalars"].data_ptr(), None, None)
+
+
 class LgarEngine:
     """N independent soil columns advanced by the gfx950 kernels.
 
@@ -171,6 +209,32 @@ class LgarEngine:
     def reset(self):
         """dpLGAR.set_internal_states() for every column."""
         self._call("state_init", C.byref(self.dims), C.byref(self._params), C.byref(self._state), self.status.data_ptr())
+
+    def snapshot(self):
+        """The column state as it stands now, as an EngineState (clones: later calls do not change it)."""
+        self._need_state()
+        return EngineState(**{nm: getattr(self, nm).clone() for nm in EngineState.FIELDS})
+
+    def _check_state(self, snap, what, N=None):
+        """`snap` is an EngineState for this engine's columns (or N of them), front slots, dtype and device."""
+        N = self.N if N is None else N
+        if not isinstance(snap, EngineState):
+            raise LgarError("%s must be an EngineState (LgarEngine.snapshot()); got %s" % (what, type(snap).__name__))
+        if snap.N != N:
+            raise LgarError("%s holds %d columns, this engine has %d" % (what, snap.N, N))
+        if snap.front_slots != self.front_slots:
+            raise LgarError("%s has front_slots = %d, this engine %d" % (what, snap.front_slots, self.front_slots))
+        if snap.dtype != self.dtype:
+            raise LgarError("%s is %s, this engine %s" % (what, snap.dtype, self.dtype))
+        if snap.device != self.status.device:
+            raise LgarError("%s is on %s, this engine on %s" % (what, snap.device, self.status.device))
+
+    def restore(self, snap):
+        """Put an EngineState back (same N, front_slots, dtype and device, else LgarError).  The run totals stay as they are."""
+        self._need_state()
+        self._check_state(snap, "the snapshot")
+        for nm in EngineState.FIELDS:
+            getattr(self, nm).copy_(getattr(snap, nm))
 
     def release_scratch(self):
         """Free the series buffers forward() keeps behind basin sums (they come back on the next such call)."""
@@ -365,21 +429,9 @@ class LgarEngine:
         if bool((status_host != 0).any()):
             self.check_status()
 
-    def tangent(self, direction, precip, pet, w_runoff=None, w_perc=None, want_series=False, forcing_group=1, share=0,
-                forcing_map=None):
-        """Forward-mode tangent from a FRESH state (set_internal_states) over the whole forcing series.
-
-        direction: {"alpha" | "n" | "ksat": [L, N] tensor} -- the parameter perturbation (missing = 0).
-        precip / pet / w_runoff / w_perc: [T, N], or all [T, Nf] with forcing_group * Nf dividing N (column c uses column
-        (c // forcing_group) % Nf of each).
-        forcing_map: a forcing.ForcingMap -- precip / pet are [T, B] and column c reads forcing column
-        forcing_map.index[c // forcing_group]; the weights are then [T, N // forcing_group] and column c reads weight column
-        c // forcing_group (they do not go through the map: the gradient of a catchment sum carries every column's own weight).
-        share = W (2..32): each group of W consecutive columns is ONE soil column along W directions; the W lanes share the
-        Geff trapezoid (LgarDims.tangent_share).
-        Returns (grad[N], tangent_runoff[T, N] or None, status[N]) with
-        grad[c] = sum_t w_runoff[t, c] * d runoff_t[c] + w_perc[t, c] * d percolation_t[c].  status != 0 marks columns whose
-        tangent integration faulted (their grad entry is not a gradient): callers must check it (autograd.parameter_vjp does)."""
+    def _tangent_inputs(self, direction, precip, pet, w_runoff, w_perc, forcing_group, share, forcing_map):
+        """What tangent() and tangent_window() take alike, on the device and checked (LgarDims' per-call fields set):
+        (precip, pet, w_runoff, w_perc, {kind: direction [L, N] or None})."""
         prep = lambda t: None if t is None else torch.as_tensor(t).to(self.device, self.dtype).contiguous()
         precip, pet = self._forcing(precip, pet, forcing_group, forcing_map)
         w_runoff, w_perc = prep(w_runoff), prep(w_perc)
@@ -404,11 +456,30 @@ class LgarEngine:
                                     % (nm, forcing_map.M, tuple(w.shape)))
             elif w is not None and w.shape != precip.shape:
                 raise LgarError("%s must be [T, N] like the forcing; got %s" % (nm, tuple(w.shape)))
-        T = precip.shape[0]
         dirs = {k: prep(direction.get(k)) for k in ("alpha", "n", "ksat")}
         for k, v in dirs.items():
             if v is not None and tuple(v.shape) != (self.L, self.N):
                 raise LgarError("direction[%r] must be [L, N]" % k)
+        return precip, pet, w_runoff, w_perc, dirs
+
+    def tangent(self, direction, precip, pet, w_runoff=None, w_perc=None, want_series=False, forcing_group=1, share=0,
+                forcing_map=None):
+        """Forward-mode tangent from a FRESH state (set_internal_states) over the whole forcing series.
+
+        direction: {"alpha" | "n" | "ksat": [L, N] tensor} -- the parameter perturbation (missing = 0).
+        precip / pet / w_runoff / w_perc: [T, N], or all [T, Nf] with forcing_group * Nf dividing N (column c uses column
+        (c // forcing_group) % Nf of each).
+        forcing_map: a forcing.ForcingMap -- precip / pet are [T, B] and column c reads forcing column
+        forcing_map.index[c // forcing_group]; the weights are then [T, N // forcing_group] and column c reads weight column
+        c // forcing_group (they do not go through the map: the gradient of a catchment sum carries every column's own weight).
+        share = W (2..32): each group of W consecutive columns is ONE soil column along W directions; the W lanes share the
+        Geff trapezoid (LgarDims.tangent_share).
+        Returns (grad[N], tangent_runoff[T, N] or None, status[N]) with
+        grad[c] = sum_t w_runoff[t, c] * d runoff_t[c] + w_perc[t, c] * d percolation_t[c].  status != 0 marks columns whose
+        tangent integration faulted (their grad entry is not a gradient): callers must check it (autograd.parameter_vjp does)."""
+        precip, pet, w_runoff, w_perc, dirs = self._tangent_inputs(direction, precip, pet, w_runoff, w_perc, forcing_group, share,
+                                                                   forcing_map)
+        T = precip.shape[0]
         dstruct = _capi.LgarParams(_ptr(dirs["alpha"]), _ptr(dirs["n"]), _ptr(dirs["ksat"]), None, None, None)
         grad = torch.zeros(self.N, dtype=self.dtype, device=self.device)
         ser = self._new_series(T, self.N, dtype=self.dtype, device=self.device) if want_series else None
@@ -418,6 +489,58 @@ class LgarEngine:
         self._call("forward_tangent", C.byref(self.dims), C.byref(self._params), C.byref(dstruct), C.byref(fo), _ptr(w_runoff),
                    _ptr(w_perc), grad.data_ptr(), _ptr(ser), st.data_ptr(), counters=tickets)
         return grad, ser, st
+
+    def tangent_window(self, direction, precip, pet, w_runoff=None, w_perc=None, start=None, keep_state=True, want_series=False,
+                       forcing_group=1, share=0, forcing_map=None):
+        """tangent() over a WINDOW of rows that may start from a carried state (lgar_forward_tangent_window, include/lgar.h).
+
+        start: None = a fresh state: tangent() itself, bit for bit.  An EngineState (snapshot() of a spun-up engine) = a
+        stop-gradient start: the result is the exact derivative, with respect to the parameters, of "forward() from this fixed
+        state over these rows"; nothing flows into the run that produced the state.  The TangentState a previous call returned
+        as `end` = carry: value state, tangent state and the gradient so far go on, and a run cut into windows leaves the bits
+        of one call (the direction must be the same one).
+        keep_state=False: no end state is stored (the last window of a backward pass).
+        Returns (grad[N], tangent_runoff[T, N] or None, status[N], end): `end` is a TangentState or None.  Columns whose start
+        state had faulted keep those fault bits in status.  This engine's own state is neither read nor written; an engine
+        made with with_state=False will do.  The other arguments are tangent()'s; with share = W the W columns of a group
+        must hold the same start values as well."""
+        precip, pet, w_runoff, w_perc, dirs = self._tangent_inputs(direction, precip, pet, w_runoff, w_perc, forcing_group, share,
+                                                                   forcing_map)
+        T, N = precip.shape[0], self.N
+        value = start.value if isinstance(start, TangentState) else start
+        if value is not None:
+            self._check_state(value, "start")
+            for nm in EngineState.FIELDS[:8] if share else ():
+                t = getattr(value, nm)
+                gw = t.reshape(t.shape[:-1] + (-1, int(share)))
+                if not bool((gw == gw[..., :1]).all()):
+                    raise LgarError("share=%d needs identical start values within each group of %d columns" % (share, share))
+        carried = start if isinstance(start, TangentState) else None
+        if carried is not None and (tuple(carried.grad.shape) != (N,) or carried.grad.dtype != self.dtype
+                                    or carried.grad.device != self.status.device):
+            raise LgarError("start carries a gradient of %s %s, this engine needs [%d] %s" % (tuple(carried.grad.shape), carried.grad.dtype, N, self.dtype))
+        z = lambda *shape, dt=self.dtype: torch.zeros(*shape, dtype=dt, device=self.device)
+        end = None
+        if keep_state:
+            F = self.front_slots
+            # (zeros: rows at and beyond a column's n_fronts are never written, and whole states are compared bit for bit)
+            end = TangentState(EngineState(depth=z(F, N), theta=z(F, N), psi=z(F, N), k=z(F, N), dzdt=z(F, N), flags=z(F, N, dt=torch.uint8),
+                                           n_fronts=z(N, dt=torch.int32), scalars=z(NSCAL, N), status=z(N, dt=torch.int32)),
+                               {nm: z(NSCAL if nm == "scalars" else F, N) for nm in _VALUE_FIELDS}, z(N))
+        structs = [None if value is None else value._struct(), None if carried is None else carried._struct(),
+                   None if end is None else end.value._struct(), None if end is None else end._struct()]
+        win = _capi.LgarTangentWindow(*[None if s is None else C.addressof(s) for s in structs], None if carried is None else carried.grad.data_ptr())
+        dstruct = _capi.LgarParams(_ptr(dirs["alpha"]), _ptr(dirs["n"]), _ptr(dirs["ksat"]), None, None, None)
+        grad = z(N) if end is None else end.grad
+        ser = self._new_series(T, N, dtype=self.dtype, device=self.device) if want_series else None
+        st = z(N, dt=torch.int32) if end is None else end.value.status
+        tickets = z(_capi.NTICKETS, dt=torch.int32)
+        fo = _capi.LgarForcing(precip.data_ptr(), pet.data_ptr(), None if forcing_map is None else forcing_map.index.data_ptr())
+        self._call("forward_tangent_window", C.byref(self.dims), C.byref(self._params), C.byref(dstruct), C.byref(fo), _ptr(w_runoff),
+                   _ptr(w_perc), C.byref(win), grad.data_ptr(), _ptr(ser), st.data_ptr(), counters=tickets)
+        if value is not None:
+            st |= value.status & _capi.ST_FAULT_MASK  # (the kernels write the status, they do not read it)
+        return grad, ser, st, end
 
     def cooperating_lanes(self):
         """Lanes per column lgar_forward uses for this engine's job (1, or 4..64 for fp64 jobs under one wave per SIMD)."""
