@@ -556,6 +556,13 @@ int32_t lgar_totals_replay(const LgarDims *dims, const LgarStepOut *stored, int3
  * op 10 geff(theta1 = x, theta2 = y) by the mixed-precision trapezoid of LgarDims.geff_mode = 1 (LGAR_F64; LGAR_F32: op 4)
  * op 11 x / y as the fast modes divide (LGAR_F64: reciprocal + Newton + correction, within an ulp of the IEEE quotient)
  * op 12 pow(x, y), 13 log2(x), 14 exp2(x) as the mixed-precision kernels evaluate them (polynomial terms combined pairwise)
+ * LGAR_F32 only (LGAR_F64: LGAR_E_ARG) -- the arithmetic of the fp32 fast mode, which ops 0-3 and 5 (IEEE divide) do not run:
+ * op 15 x / y as x * v_rcp_f32(y), 16 sqrt(x) as v_sqrt_f32
+ * op 17 theta_from_h(x), 18 se_from_h(x), 19 k_from_se(x), 20 h_from_se(x), 21 aet(psi = x, pet = y, dt_h = z) with that
+ *      quotient and the v_log_f32 / v_exp_f32 pow
+ * op 22 the fp32 trapezoid between two heads h_i = x, h_f = y (calc_dzdt's site: the heads are the fronts' own psi)
+ * op 23 the closed-form Geff(theta1 = x, theta2 = y)                        (lgar/green_ampt.py:85-98)
+ * (LGAR_F32: ops 7 and 8 are the raw v_log_f32 and v_exp_f32, op 9 the pow made of them)
  * alpha, n, ksat, theta_e, theta_r: [n] per-item soil parameters. */
 int32_t lgar_leaf_batch(int32_t op, int32_t n_items, const void *x, const void *y, double z, const void *alpha,
                         const void *n, const void *ksat, const void *theta_e, const void *theta_r, int32_t nint,

@@ -9,59 +9,15 @@
 #include "lgar_geff.hpp"
 #include "lgar_host.hpp"
 #include "lgar_launch.hpp"
+#include "lgar_leaf.hpp"
 #include "lgar_moisture.hpp"
 
 namespace lgar {
 
-template <typename R> struct LeafArgs {
-  int op, n, nint;
-  const R *x, *y, *alpha, *nn, *ksat, *te, *tr;
-  R z, wp_psi;
-  R *out;
-};
-
 template <typename R> __global__ void lgar_leaf_kernel(LeafArgs<R> a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n) return;
-  LayerK<R> l;
-  l.alpha = a.alpha[i];
-  l.n = a.nn[i];
-  l.m = R(1.0) - (R(1.0) / l.n);
-  l.inv_m = R(1.0) / l.m;
-  l.inv_n = R(1.0) / l.n;
-  l.ksat = a.ksat[i];
-  l.te = a.te[i];
-  l.tr = a.tr[i];
-  const R x = a.x[i];
-  const R y = a.y ? a.y[i] : R(0);
-  R r = R(0);
-  switch (a.op) {
-    case 0: r = theta_from_h(l, x); break;
-    case 1: r = se_from_h(l, x); break;
-    case 2: r = k_from_se(l, x); break;
-    case 3: r = h_from_se(l, x); break;
-    case 4: r = geff(l, x, y, a.nint); break;
-    case 5: r = aet_fn(l, y, a.z, x, a.wp_psi); break;
-    case 6: r = geff_literal<R, ScalarKind<R>::f64 ? POL_LIBRARY : POL_LEAN>(l, x, y, a.nint); break;
-    case 7: r = lg2p(x); break;
-    case 8: r = ex2p(x); break;
-    case 9: r = pw(x, y); break;
-    case 10:
-      if constexpr (ScalarKind<R>::f64) r = geff_mixed(l.alpha, l.n, l.m, l.inv_m, l.inv_n, l.ksat, l.te, l.tr, x, y, a.nint);
-      else r = geff(l, x, y, a.nint);
-      break;
-    case 11: r = dv<POL_LEAN>(x, y); break;   // the fast modes' quotient (double precision: lean_div)
-    case 12: r = pwp<POL_MIXED>(x, y); break;  // the mixed-precision kernels' pow (pairwise-combined polynomials)
-    case 13:
-      if constexpr (ScalarKind<R>::f64) r = lg2e(x);
-      else r = lg2p(x);
-      break;
-    case 14:
-      if constexpr (ScalarKind<R>::f64) r = ex2e(x);
-      else r = ex2p(x);
-      break;
-  }
-  a.out[i] = r;
+  a.out[i] = leaf_eval(a, i);
 }
 
 static int check_state(const LgarParams *p, const LgarState *s, const int32_t *status) {
@@ -300,8 +256,9 @@ int32_t lgar_catchment_spread(const double *grad, int32_t n_rows, int32_t n_catc
 int32_t lgar_leaf_batch(int32_t op, int32_t n_items, const void *x, const void *y, double z, const void *alpha,
                         const void *n, const void *ksat, const void *theta_e, const void *theta_r, int32_t nint,
                         double wilting_point_psi, void *out, int32_t dtype, void *stream) {
-  if (op < 0 || op > 14 || n_items <= 0 || !x || !alpha || !n || !ksat || !theta_e || !theta_r || !out) return LGAR_E_ARG;
-  if ((op == 4 || op == 5 || op == 6 || op == 10) && !y) return LGAR_E_ARG;
+  if (op < 0 || op > LEAF_OP_LAST || n_items <= 0 || !x || !alpha || !n || !ksat || !theta_e || !theta_r || !out) return LGAR_E_ARG;
+  if (op >= LEAF_OP_F32_FIRST && dtype != LGAR_F32) return LGAR_E_ARG;  // the fp32 fast mode's arithmetic: float only
+  if ((op == 4 || op == 5 || op == 6 || op == 10 || op == 15 || op == 21 || op == 22 || op == 23) && !y) return LGAR_E_ARG;
   const unsigned grid = (unsigned)((n_items + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == LGAR_F64) {

@@ -717,7 +717,10 @@ def leaf_batch(op, x, y=None, z=0.0, *, alpha, n, ksat, theta_e, theta_r, nint=1
     dev = torch.device(device)
     lib = _capi.open_library(dev, _NO_GPU)
     ops = {"theta_from_h": 0, "se_from_h": 1, "k_from_se": 2, "h_from_se": 3, "geff": 4, "aet": 5, "geff_literal": 6,
-           "log2": 7, "exp2": 8, "pow": 9, "geff_mixed": 10, "div": 11, "pow_pairwise": 12, "log2_pairwise": 13, "exp2_pairwise": 14}
+           "log2": 7, "exp2": 8, "pow": 9, "geff_mixed": 10, "div": 11, "pow_pairwise": 12, "log2_pairwise": 13, "exp2_pairwise": 14,
+           # float32 only: the fp32 fast mode's arithmetic (a * v_rcp_f32(b), v_sqrt_f32, v_log_f32 / v_exp_f32 pow)
+           "div_rcp32": 15, "sqrt": 16, "theta_from_h_rcp32": 17, "se_from_h_rcp32": 18, "k_from_se_rcp32": 19,
+           "h_from_se_rcp32": 20, "aet_rcp32": 21, "geff_from_heads": 22, "geff_closed": 23}
     prep = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float64).to(dev, dtype).contiguous()
     x, y, alpha, n, ksat, theta_e, theta_r = map(prep, (x, y, alpha, n, ksat, theta_e, theta_r))
     out = torch.empty_like(x)
