@@ -568,6 +568,27 @@ int32_t lgar_leaf_batch(int32_t op, int32_t n_items, const void *x, const void *
                         const void *n, const void *ksat, const void *theta_e, const void *theta_r, int32_t nint,
                         double wilting_point_psi, void *out, int32_t dtype, void *stream);
 
+/* Tangent leaf kernels (known-answer tests of the dual-number arithmetic of the tangent kernels), element-wise over n items: the
+ * leaf's value and ONE directional derivative, along the seeds d_alpha, d_n, d_ksat, d_theta_e, d_theta_r, d_x, d_y ([n] each; a
+ * null pointer is a seed of 0).  m = 1 - 1/n, 1/m and 1/n are formed in dual numbers as the tangent kernels form them.
+ * policy: 0 POL_LEAN (the fast tangent kernels), 1 POL_LIBRARY (the verification kernels) -- read by ops 0-3, 5, 23, 24.
+ * op numbers are lgar_leaf_batch's where the op exists there:
+ * op 0 theta_from_h(x), 1 se_from_h(x), 2 k_from_se(x), 3 h_from_se(x), 5 aet(psi = x, pet = y, dt_h = z),
+ * op 23 the closed-form Geff(theta1 = x, theta2 = y), 24 se_from_theta(x)
+ * op 4 geff(theta1 = x, theta2 = y): the fused trapezoid with its hand-derived node tangent
+ * op 6 the same trapezoid operation by operation, POL_LIBRARY
+ * primitives of the dual numbers (soil parameters unused but required; seeds d_x, d_y):
+ * op 7 lg2p(x), 8 ex2p(x), 9 pw(x, y), 11 dv<POL_LEAN>(x, y), 16 sq(x), 25 pwx<true>(x, y) (the library pow),
+ * op 26 dv<POL_LEAN>(x, real y), 27 dv<POL_LEAN>(real x, y), 28 x / y (operator/), 29 lg2(x), 30 ex2(x), 31 mn(x, y), 32 ab(x)
+ * share = W in 2 .. 32 (op 4, LGAR_F64 only; 0: every lane on its own): the trapezoid shared by W lanes as the tangent kernels
+ * share it (LgarDims.tangent_share) -- one-wave workgroups, floor(64 / W) groups of W adjacent lanes, one item per group, lane r of
+ * a group along direction r: the seeds and both outputs are then [n][W]. */
+int32_t lgar_leaf_tangent_batch(int32_t op, int32_t policy, int32_t share, int32_t n_items, const void *x, const void *y, double z,
+                                const void *alpha, const void *n, const void *ksat, const void *theta_e, const void *theta_r,
+                                const void *d_alpha, const void *d_n, const void *d_ksat, const void *d_theta_e,
+                                const void *d_theta_r, const void *d_x, const void *d_y, int32_t nint, double wilting_point_psi,
+                                void *out_value, void *out_tangent, int32_t dtype, void *stream);
+
 /* Measurement only (no reference counterpart): vector-ALU issue-rate probe, the compute-side roof bench.py prices the
  * path against (the path is VALU-bound: ~10^3 flop per algorithmic byte).  Launches n_workgroups one-wave workgroups,
  * each running `iters` iterations of lgar_valu_probe_insts(op) instructions of kind `op`; lds_bytes_per_workgroup sets the resident waves

@@ -104,7 +104,9 @@ template <typename R> __device__ __forceinline__ Dual<R> sq(const Dual<R> &x) {
   return Dual<R>(v, (v > R(0)) ? dquot(x.d, R(2) * v) : R(0));
 }
 template <typename R> __device__ __forceinline__ Dual<R> ab(const Dual<R> &x) {
-  return Dual<R>(ab(x.v), (x.v > R(0)) ? x.d : ((x.v < R(0)) ? -x.d : R(0)));
+  // (sign(x) dx: 0 at 0 -- and NaN at NaN, as torch has it: a trapezoid from outside the domain must not hand a NaN value on with
+  // a tangent of 0, which is what the literal trapezoid did -- geff_literal from theta > theta_e, tests/test_leaf_tangent_host.py)
+  return Dual<R>(ab(x.v), (x.v > R(0)) ? x.d : ((x.v < R(0)) ? -x.d : ((x.v == R(0)) ? R(0) : x.v)));
 }
 template <typename R> __device__ __forceinline__ Dual<R> mn(const Dual<R> &a, const Dual<R> &b) {
   if (a.v < b.v) return a;
@@ -382,7 +384,9 @@ __device__ __forceinline__ void geff_shared_blocks_w(const LayerK<Dual<double>> 
   // d(alpha h_j) = c0 + j c1 with the node's head h_j = h_0 + j dh.  c0 and c1 are formed FIRST: for the alpha direction
   // alpha h does not depend on alpha at all (h = f(Se) / alpha), the two products in each cancel, and they must cancel before
   // anything is summed -- grouped by input instead (d alpha sum A1 h + alpha sum A1 dh_j) the big sums cancel to ~1e-8 of the
-  // gradient (measured against the unshared launch; now ~1e-12).
+  // gradient (measured against the unshared launch; now 1e-15 ... 1e-14 of it as a rule and up to 1e-10 for the narrowest
+  // groups -- 8.5e-11 for W = 2, 1e-11 for W = 3: tests/test_gpu_leaf_tangent.py, DESIGN.md section 4 -- not the ~1e-12 once
+  // stated here).
   const double c0 = l.alpha.d * h2.v + l.alpha.v * h2.d;
   const double c1 = l.alpha.d * dh.v + l.alpha.v * dh.d;
   const double sumKd = c0 * S[0] + c1 * S[1] + nm1.d * S[2] + half_m.d * S[3] + l.ksat.d * S[4];

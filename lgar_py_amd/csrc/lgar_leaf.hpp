@@ -1,8 +1,9 @@
 // lgar_leaf.hpp -- the element-wise leaf dispatcher of the known-answer tests (lgar_leaf_batch, include/lgar.h): one function
 // of an item's soil parameters and operands per op number.  The leaf kernel (lgar_kernels.hip) and the tests' host build of
 // the device code (tests/leaf_host, -DLGAR_DEVSIM) both call leaf_eval, so what a test pins on the host is what the kernel runs.
+// leaf_tangent_eval is the same for the dual numbers of the tangent kernels (lgar_leaf_tangent_batch): value and one tangent.
 #pragma once
-#include "lgar_geff.hpp"
+#include "lgar_dual.hpp"
 
 namespace lgar {
 
@@ -21,9 +22,7 @@ template <typename R> __device__ __forceinline__ R leaf_eval(const LeafArgs<R> &
   LayerK<R> l;
   l.alpha = a.alpha[i];
   l.n = a.nn[i];
-  l.m = R(1.0) - (R(1.0) / l.n);
-  l.inv_m = R(1.0) / l.m;
-  l.inv_n = R(1.0) / l.n;
+  derive_layer(l.n, l.m, l.inv_m, l.inv_n);
   l.ksat = a.ksat[i];
   l.te = a.te[i];
   l.tr = a.tr[i];
@@ -74,6 +73,96 @@ template <typename R> __device__ __forceinline__ R leaf_eval(const LeafArgs<R> &
       break;
   }
   return r;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the tangent leaves (lgar_leaf_tangent_batch, include/lgar.h): the same functions of dual numbers
+// ---------------------------------------------------------------------------------------------
+constexpr int LEAF_NSEED = 7;  // d_alpha, d_n, d_ksat, d_theta_e, d_theta_r, d_x, d_y
+template <typename R> struct LeafTangentArgs {
+  int op, pol, share, n, nint;  // share: 0, or the W lanes of a group that carry one item along W directions
+  const R *x, *y, *alpha, *nn, *ksat, *te, *tr;
+  const R *seed[LEAF_NSEED];  // [n] each ([n][share] with share): a null pointer is a seed of 0
+  R z, wp_psi;
+  R *value, *tangent;  // [n] ([n][share])
+};
+constexpr int LEAF_TOP_LAST = 32;
+// ops that take the arithmetic policy (POL_LEAN / POL_LIBRARY), ops that read y, the fused trapezoid
+__host__ __device__ inline bool leaf_tangent_op_exists(int op) {
+  return (op >= 0 && op <= 9) || op == 11 || op == 16 || (op >= 23 && op <= LEAF_TOP_LAST);
+}
+__host__ __device__ inline bool leaf_tangent_op_needs_y(int op) {
+  return op == 4 || op == 5 || op == 6 || op == 9 || op == 11 || op == 23 || (op >= 25 && op <= 28) || op == 31;
+}
+constexpr int LEAF_TOP_GEFF = 4;
+
+template <typename R, int POL>
+__device__ __forceinline__ Dual<R> leaf_tangent_policy_op(const LeafTangentArgs<R> &a, const LayerK<Dual<R>> &l, const Dual<R> &x,
+                                                          const Dual<R> &y) {
+  using S = Dual<R>;
+  switch (a.op) {
+    case 0: return theta_from_h<S, POL>(l, x);
+    case 1: return se_from_h<S, POL>(l, x);
+    case 2: return k_from_se<S, POL>(l, x);
+    case 3: return h_from_se<S, POL>(l, x);
+    case 5: return aet_fn<S, POL>(l, y, a.z, x, a.wp_psi);
+    case 23: return geff_closed<S, POL>(l, x, y);
+    default: return se_from_theta(l, x);  // 24
+  }
+}
+
+// direction `k` (an index into the seed arrays: the item, or item * share + lane of the group) of item i.  xchg, W: the wave's
+// exchange buffer and the group width of the shared trapezoid (op 4 in double precision only), as Column::capillary_drive passes them.
+template <typename R>
+__device__ __forceinline__ Dual<R> leaf_tangent_eval(const LeafTangentArgs<R> &a, int i, int k, R *xchg = nullptr, int W = 0) {
+  using S = Dual<R>;
+  auto seed = [&](int j) { return a.seed[j] ? a.seed[j][k] : R(0); };
+  LayerK<S> l;
+  l.alpha = S(a.alpha[i], seed(0));
+  l.n = S(a.nn[i], seed(1));
+  derive_layer(l.n, l.m, l.inv_m, l.inv_n);
+  l.ksat = S(a.ksat[i], seed(2));
+  l.te = S(a.te[i], seed(3));
+  l.tr = S(a.tr[i], seed(4));
+  const S x(a.x[i], seed(5));
+  const S y(a.y ? a.y[i] : R(0), seed(6));
+  (void)xchg; (void)W;
+  switch (a.op) {
+    case 4:
+      if constexpr (ScalarKind<R>::f64) {
+        if (W >= 2) return geff_fused<S>(l, x, y, a.nint, xchg, W);
+      }
+      return geff(l, x, y, a.nint);
+    case 6: return geff_literal<S, POL_LIBRARY>(l, x, y, a.nint);
+    case 7: return lg2p(x);
+    case 8: return ex2p(x);
+    case 9: return pw(x, y);
+    case 11: return dv<POL_LEAN>(x, y);
+    case 16: return sq(x);
+    case 25: return pwx<true>(x, y);
+    case 26: return dv<POL_LEAN>(x, y.v);
+    case 27: return dv<POL_LEAN>(x.v, y);
+    case 28: return x / y;
+    case 29: return lg2(x);
+    case 30: return ex2(x);
+    case 31: return mn(x, y);
+    case 32: return ab(x);
+    default:
+      return a.pol == POL_LIBRARY ? leaf_tangent_policy_op<R, POL_LIBRARY>(a, l, x, y) : leaf_tangent_policy_op<R, POL_LEAN>(a, l, x, y);
+  }
+}
+// the argument checks of lgar_leaf_tangent_batch, shared by the library and the tests' host build (which has no shared trapezoid)
+template <bool HOST = false>
+inline int leaf_tangent_check(int op, int policy, int share, int n_items, const void *x, const void *y, const void *alpha, const void *n,
+                              const void *ksat, const void *theta_e, const void *theta_r, const void *out_value, const void *out_tangent,
+                              int dtype) {
+  if (!leaf_tangent_op_exists(op) || n_items <= 0 || !x || !alpha || !n || !ksat || !theta_e || !theta_r || !out_value || !out_tangent)
+    return LGAR_E_ARG;
+  if (dtype != LGAR_F32 && dtype != LGAR_F64) return LGAR_E_ARG;
+  if (policy != POL_LEAN && policy != POL_LIBRARY) return LGAR_E_ARG;
+  if (leaf_tangent_op_needs_y(op) && !y) return LGAR_E_ARG;
+  if (share != 0 && (HOST || share < 2 || share > 32 || dtype != LGAR_F64 || op != LEAF_TOP_GEFF)) return LGAR_E_ARG;
+  return 0;
 }
 
 }  // namespace lgar

@@ -194,6 +194,16 @@ template <typename S> struct LayerK {
   S alpha, n, m, inv_m, inv_n, ksat, te, tr;
 };
 
+// the derived parameters of a layer, m = 1 - 1/n, 1/m and 1/n, in the scalar type S (for dual numbers: with their tangents along
+// dn).  The tangent kernels (tangent_lane) and the leaf dispatchers (lgar_leaf.hpp) both form them here: what a leaf test pins is
+// what the kernels run.
+template <typename S> __device__ __forceinline__ void derive_layer(const S &n, S &m, S &inv_m, S &inv_n) {
+  using R = real_t<S>;
+  m = R(1.0) - (R(1.0) / n);
+  inv_m = R(1.0) / m;
+  inv_n = R(1.0) / n;
+}
+
 template <typename S, int NL> struct ColParams {
   S alpha[NL], n[NL], m[NL], inv_m[NL], inv_n[NL], ksat[NL], te[NL], tr[NL], thick[NL], cum[NL];
 };

@@ -133,9 +133,7 @@ __device__ __forceinline__ void tangent_lane(const LGAR_KARG TArgs<R> *ap, size_
     P.te[k] = S(a.theta_e[o]);
     P.tr[k] = S(a.theta_r[o]);
     P.thick[k] = S(a.thick[o]);
-    P.m[k] = R(1.0) - (R(1.0) / P.n[k]);
-    P.inv_m[k] = R(1.0) / P.m[k];
-    P.inv_n[k] = R(1.0) / P.n[k];
+    derive_layer(P.n[k], P.m[k], P.inv_m[k], P.inv_n[k]);
     P.cum[k] = (k == 0) ? P.thick[0] : P.cum[(k > 0) ? k - 1 : 0] + P.thick[k];
   }
   Column<S, NL, FMAX, MODE> col(P, &ap->G, make_view<S, FMAX>(&lds.f[0][0][0], &lds.fl[0][0], lane));

@@ -728,3 +728,35 @@ def leaf_batch(op, x, y=None, z=0.0, *, alpha, n, ksat, theta_e, theta_r, nint=1
                  _ptr(theta_e), _ptr(theta_r), int(nint), float(wilting_point_psi), _ptr(out),
                  _capi.dtype_code(dtype, _DTYPES))
     return out
+
+
+LEAF_TANGENT_OPS = {"theta_from_h": 0, "se_from_h": 1, "k_from_se": 2, "h_from_se": 3, "geff": 4, "aet": 5, "geff_literal": 6,
+                    "lg2p": 7, "ex2p": 8, "pw": 9, "dv": 11, "sq": 16, "geff_closed": 23, "se_from_theta": 24, "pwx": 25,
+                    "dv_dual_real": 26, "dv_real_dual": 27, "quotient": 28, "lg2": 29, "ex2": 30, "mn": 31, "ab": 32}
+LEAF_SEEDS = ("alpha", "n", "ksat", "theta_e", "theta_r", "x", "y")
+
+
+def leaf_tangent_batch(op, x, y=None, z=0.0, *, alpha, n, ksat, theta_e, theta_r, seeds=None, policy="lean", share=0, nint=120,
+                       wilting_point_psi=15495.0, dtype=torch.float64, device="cuda:0"):
+    """Element-wise tangent leaf kernels (known-answer tests): (value, tangent) of `op` along `seeds`, a dict of LEAF_SEEDS
+    names -> [n] (a name left out is a seed of 0); with share = W, seeds and both results are [n, W].  See
+    lgar_leaf_tangent_batch in include/lgar.h."""
+    dev = torch.device(device)
+    lib = _capi.open_library(dev, _NO_GPU)
+    prep = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float64).to(dev, dtype).contiguous()
+    x, y, alpha, n, ksat, theta_e, theta_r = map(prep, (x, y, alpha, n, ksat, theta_e, theta_r))
+    seeds = dict(seeds or {})
+    unknown = set(seeds) - set(LEAF_SEEDS)
+    if unknown:
+        raise ValueError("unknown seeds %s" % sorted(unknown))
+    shape = (x.numel(), int(share)) if share else (x.numel(),)
+    sd = [prep(seeds.get(k)) for k in LEAF_SEEDS]
+    for s in sd:
+        if s is not None and tuple(s.shape) != shape:
+            raise ValueError("a seed has shape %s, not %s" % (tuple(s.shape), shape))
+    value = torch.empty(shape, dtype=dtype, device=dev)
+    tangent = torch.empty(shape, dtype=dtype, device=dev)
+    _capi.launch(lib, "leaf_tangent_batch", dev, LEAF_TANGENT_OPS[op], {"lean": 0, "library": 1}[policy], int(share), x.numel(),
+                 _ptr(x), _ptr(y), float(z), _ptr(alpha), _ptr(n), _ptr(ksat), _ptr(theta_e), _ptr(theta_r), *[_ptr(s) for s in sd],
+                 int(nint), float(wilting_point_psi), _ptr(value), _ptr(tangent), _capi.dtype_code(dtype, _DTYPES))
+    return value, tangent

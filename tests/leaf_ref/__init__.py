@@ -286,11 +286,19 @@ def stmt_se_from_h(s, h):
     return (1 + (s.alpha * h) ** s.n) ** (-s.m_exact)
 
 
-def stmt_kr_from_se(s, se):
+def _sqrt(x):
+    """sqrt of an mpmath number or of anything that brings its own (the dual numbers of leaf_ref.tangent)."""
+    return x.sqrt() if hasattr(x, "sqrt") else mpmath.sqrt(x)
+
+
+def stmt_kr_from_se(s, se, nudge=True):
+    """nudge=False: without calc_k_from_se's b + 1e-12 (what the fused trapezoid node leaves out: leaf_ref.tangent)."""
     if se == 0:
         return mpmath.mpf(0)
-    b = _nudge(1 - se ** (1 / s.m_exact))
-    return mpmath.sqrt(se) * (1 - b ** s.m_exact) ** 2
+    b = 1 - se ** (1 / s.m_exact)
+    if nudge:
+        b = _nudge(b)
+    return _sqrt(se) * (1 - b ** s.m_exact) ** 2
 
 
 def stmt_k_from_se(s, se):
@@ -304,24 +312,26 @@ def stmt_h_from_se(s, se):
     return b ** (1 / s.n) / s.alpha
 
 
-def stmt_trapezoid(s, h_i, h_f, nint, k_first=None):
+def stmt_trapezoid(s, h_i, h_f, nint, k_first=None, node_nudge=True):
     """|sum_j (K_j-1 + K_j) dh / 2| / Ksat, nodes h_i + j dh; k_first: K_0 / Ksat where it is not K(Se(h_i)).  Also returns the
-    distance of the node nearest the 0.1 cm cut from it, relative (a node AT the cut would make the sum discontinuous)."""
+    distance of the node nearest the 0.1 cm cut from it, relative (a node AT the cut would make the sum discontinuous).
+    node_nudge=False: the nodes above the cut without calc_k_from_se's nudge (those under it are K(Se = 1), nudged, either way)."""
     dh = (h_f - h_i) / nint
     k_prev = stmt_kr_from_se(s, stmt_se_from_h(s, h_i)) if k_first is None else k_first
     g, near = mpmath.mpf(0), mpmath.inf
     for j in range(1, nint + 1):
         h = h_f if j == nint else h_i + j * dh
         near = min(near, abs(h - mpmath.mpf("0.1")) / mpmath.mpf("0.1"))
-        k = stmt_kr_from_se(s, stmt_se_from_h(s, h))
+        k = stmt_kr_from_se(s, stmt_se_from_h(s, h), nudge=node_nudge or bool(abs(h) < mpmath.mpf("0.1")))
         g += (k_prev + k) * dh / 2
         k_prev = k
     return abs(g), float(near)
 
 
-def stmt_geff(s, theta1, theta2, nint):
+def stmt_geff(s, theta1, theta2, nint, node_nudge=True):
     se_i, se_f = stmt_se_from_theta(s, theta1), stmt_se_from_theta(s, theta2)
-    return stmt_trapezoid(s, stmt_h_from_se(s, se_i), stmt_h_from_se(s, se_f), nint, k_first=stmt_kr_from_se(s, se_i))
+    return stmt_trapezoid(s, stmt_h_from_se(s, se_i), stmt_h_from_se(s, se_f), nint, k_first=stmt_kr_from_se(s, se_i),
+                          node_nudge=node_nudge)
 
 
 def stmt_geff_closed(s, theta1, theta2):

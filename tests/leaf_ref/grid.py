@@ -92,6 +92,118 @@ def inputs():
     return S, res
 
 
+# The shared trapezoid (geff_shared_blocks_w) takes floor(n_safe / W) full blocks and one of n_safe % W nodes, and declines for
+# n_safe < W.  Counts that put every width of tests/test_gpu_leaf_tangent.py (2, 3, 5, 6, 8, 9, 12, 15, 18, 32) into each case:
+# 1 is below every width; 90 is a multiple of 2, 3, 5, 6, 9, 15, 18 and 96 of 8, 12, 32; 97 is prime.
+DRIFT_MARGIN = 0.1
+SHARE_COUNTS = (1, 90, 96, 97)
+SHARE_SOILS = ("vg_table_00", "vg_table_05", "vg_table_11", "synthetic_n1.09", "synthetic_n3.5", "perturbed_layer_1")
+
+
+def tangent_inputs():
+    """(soils [S, 5] float64, {function of leaf_ref.tangent.FUNCTIONS: (soil index, x, y, z, f32ok)}) -- the points of
+    tests/golden/leaf_tangent/leaf_tangent_ref.npz.  The fp32 fixture's soils and kinds of points, in float64: every point with
+    f32ok set is an fp32 number (the fp32 run takes the same point), the others exist in double precision only -- the doubles
+    either side of the 0.1 cm cut, Se = 1 - 2^-k beyond k = 24, the two doubles either side of each |base| = 1e-8 switch.
+    Within a soil the points of a function are sorted along its operand (x; for the AET: psi within one (dt, pet); the theta
+    pairs in the fp32 fixture's order), so that a point's neighbours in the arrays are its neighbours on that axis."""
+    from leaf_ref import tangent as TG
+    mpmath.mp.dps = R.DPS
+    S = soils().astype(np.float64)
+    kats = np.load(os.path.join(GOLDEN, "leaf_kats.npz"))
+    D = np.float64
+    cut32, cut64 = F(0.1), D(0.1)
+    hs32 = [np.nextafter(cut32, F(0)), cut32] + list(np.geomspace(0.2, 1e6, 20).astype(F))
+    hs64 = [np.nextafter(cut64, D(0)), cut64, np.nextafter(cut64, D(1))]
+    out = {fn: [] for fn in TG.FUNCTIONS}
+
+    def put(fn, si, xs32, xs64, y=0.0, z=0.0):
+        pts = sorted(set((float(v), 1) for v in xs32) | set((float(v), 0) for v in xs64 if float(v) not in set(float(w) for w in xs32)))
+        out[fn] += [(si, v, y, z, ok) for v, ok in pts]
+
+    for si, row in enumerate(S):
+        soil = R.Soil(*row)  # (the rows are fp32 numbers: Soil's rounding changes nothing)
+        te, tr = row[3], row[4]
+        put("theta_from_h", si, hs32, hs64)
+        put("se_from_h", si, hs32, hs64)
+        m = soil.m_exact
+        se32 = list(np.geomspace(1e-6, 0.9, 14).astype(F)) + list(kats["ses"].astype(F)) + [F(1)] + [F(1) - F(2.0 ** -k) for k in (20, 22, 24)]
+        se64 = [D(1) - D(2.0) ** -k for k in range(26, 53, 2)] + [D(1) - D(2.0) ** -52]
+        # the doubles either side of the switches: 1 - Se^(1/m) = 1e-8 (k_from_se), Se^(-1/m) - 1 = 1e-8 (h_from_se)
+        for se_sw in ((1 - mpmath.mpf("1e-8")) ** m, (1 + mpmath.mpf("1e-8")) ** (-m)):
+            v = D(float(se_sw))
+            se64 += [np.nextafter(v, D(0)), np.nextafter(v, D(1))]
+        # every other soil: one Se beyond 1 -- outside the domain: negative pow bases, NaN in the statement and in the kernels
+        outside = [F(1.25)] if si % 2 == 0 else []
+        put("k_from_se", si, se32 + outside, se64)
+        put("h_from_se", si, se32 + outside, se64)
+        # The AET's clamp, torch.clamp(a, 0, pet) with a = pet dt / (1 + (psi / psi_wp)^3).  The leaf_kats operands stay strictly
+        # inside (0, pet); added: psi = -2 psi_wp (1 + r^3 = -7: a < 0, the LOWER clamp, every partial 0), psi = 0 (with dt = 1 an
+        # exact TIE, a == pet: the argument's own tangent, which is d pet as well), and dt = 2 at psi = 0, 0.5 and psi_wp / 4 (a > pet,
+        # the UPPER clamp: d/dpet = 1, every other partial 0).
+        psi_wp = float(R.stmt_h_from_se(soil, R.stmt_se_from_theta(soil, (soil.tr + mpmath.mpf("0.75") * (soil.te - soil.tr) + R.stmt_theta_from_h(soil, R.M(R.WP_PSI))) / 2)))
+        for dt in kats["aet_dts"]:
+            for pet in kats["aet_pets"][::2]:
+                put("aet", si, list(kats["aet_psis"].astype(F)) + [F(0), F(-2.0 * psi_wp)], [], float(F(pet)), float(F(dt)))
+        for pet in kats["aet_pets"][::2]:
+            put("aet", si, [F(0), F(0.5), F(0.25 * psi_wp)], [], float(F(pet)), 2.0)
+        thetas = [te if f == 1.0 else min(F(tr + F(f) * F(te - tr)), F(te)) for f in FRACTIONS]
+        put("se_from_theta", si, [F(t) for t in thetas], [])
+        for a in range(len(thetas)):
+            for b in range(a + 1, len(thetas)):
+                out["geff_closed"].append((si, float(thetas[a]), float(thetas[b]), 0.0, 1))
+                # The trapezoid's heads are a running sum, h2 += dh, in the reference and in the kernels alike: nint additions at
+                # the magnitude of h_i, each rounded.  Where what they can add up to, nint 2^-52 h_i, comes near the distance of
+                # the wet end's head from the cut, the last node lands on either side of it -- or below zero: saturated -- by the
+                # luck of the roundings, and the double-precision sum is no function of its inputs any more (n = 1.09 from
+                # Se = 0.02: h_i = 4e20 cm, additions rounded by 6e4 cm; the fused and the literal kernel differ by a factor 1e9
+                # there, the reference raises or is off by 200 x).  Such pairs are left out (DRIFT_MARGIN of that distance).
+                h_i, h_f = (R.stmt_h_from_se(soil, R.stmt_se_from_theta(soil, R.M(t))) for t in (thetas[a], thetas[b]))
+                if NINT * mpmath.ldexp(1, -52) * h_i > DRIFT_MARGIN * abs(h_f - mpmath.mpf("0.1")):
+                    continue
+                for fn in ("geff", "geff_literal"):
+                    out[fn].append((si, float(thetas[a]), float(thetas[b]), 0.0, 1))
+        if SOIL_NAMES[si] == "synthetic_n3.5":
+            # trapezoids up to theta_e whose last interior node lies in 0.1 < h < 0.13 cm, where (alpha h)^n <= 1e-8 ABOVE the cut:
+            # the one place on this grid where calc_k_from_se's nudge, which the fused node leaves out, changes a node
+            for f in (0.92, 0.94, 0.96):
+                for fn in ("geff", "geff_literal", "geff_closed"):
+                    out[fn].append((si, float(F(tr + F(f) * F(te - tr))), float(te), 0.0, 1))
+        if SOIL_NAMES[si] in SHARE_SOILS:
+            # trapezoids up to theta_e whose count of leading nodes a whole interval above the cut (geff_fused's n_safe, from
+            # jf = (h_i - 0.1) / -dh - 1) is c, for the shared trapezoid's cases: theta_1 from the head h_i at which jf = c + 1/2
+            # ... and one pair from beyond theta_e (Se > 1: outside the domain, NaN)
+            for fn in ("geff", "geff_literal"):
+                out[fn].append((si, float(F(te + F(0.05))), float(te), 0.0, 1))
+            h_f = R.stmt_h_from_se(soil, mpmath.mpf(1))
+            for c in SHARE_COUNTS:
+                h_i = (mpmath.mpf(12) - (c + 1.5) * h_f) / (mpmath.mpf("118.5") - c)
+                t1 = float(soil.tr + R.stmt_se_from_h(soil, h_i) * (soil.te - soil.tr))
+                assert tr < t1 < te, (SOIL_NAMES[si], c)
+                for fn in ("geff", "geff_literal"):
+                    out[fn].append((si, t1, float(te), 0.0, 0))
+    rng = np.random.default_rng(20251)
+    pw_pts = [(x, y) for x in np.geomspace(1e-6, 1e3, 12).astype(F) for y in (-5.5, -1.0, 0.0826, 0.5, 1.0, 3.7) if abs(y * np.log2(x)) <= 100]
+    pw_pts += [(0.0, 2.0), (0.0, 0.5)]  # x = 0: value and tangent 0
+    ab2 = (10.0 ** rng.uniform(-12, 12, (96, 2)) * rng.choice([-1.0, 1.0], (96, 2))).astype(F)
+    for fn in ("pw", "pwx"):
+        out[fn] = [(0, float(x), float(F(y)), 0.0, 1) for x, y in pw_pts]
+    for fn in ("dv", "dv_dual_real", "dv_real_dual", "quotient"):
+        out[fn] = [(0, float(a), float(b), 0.0, 1) for a, b in ab2]
+    pos = np.sort(np.abs(ab2[:, 0]))
+    for fn in ("sq", "lg2", "lg2p"):
+        out[fn] = [(0, float(a), 0.0, 0.0, 1) for a in pos]
+    for fn in ("ex2", "ex2p"):
+        out[fn] = [(0, float(t), 0.0, 0.0, 1) for t in np.sort(rng.uniform(-120.0, 120.0, 96).astype(F))]
+    out["mn"] = [(0, float(a), float(b), 0.0, 1) for a, b in ab2] + [(0, 2.5, 2.5, 0.0, 1), (0, -1.0, -1.0, 0.0, 1)]  # ties: half each
+    out["ab"] = [(0, float(a), 0.0, 0.0, 1) for a in np.sort(ab2[:, 0])] + [(0, 0.0, 0.0, 0.0, 1)]
+    res = {}
+    for fn, pts in out.items():
+        a = np.array(pts, dtype=np.float64)
+        res[fn] = (a[:, 0].astype(np.int16), a[:, 1].copy(), a[:, 2].copy(), a[:, 3].copy(), a[:, 4].astype(np.uint8))
+    return S, res
+
+
 def evaluate(fn, S, si, x, y, z):
     """(ref[N] float64, coef[N, 6] float64, near[N], gap[N]) of the points."""
     mpmath.mp.dps = R.DPS
