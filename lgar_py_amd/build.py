@@ -15,9 +15,8 @@ UNITS = [("lgar_kernels.hip", [], ""), ("lgar_probe.hip", [], ""), ("lgar_moistu
          ("lgar_route.hip", [], ""), ("lgar_score.hip", [], ""), ("lgar_network.hip", [], ""), ("lgar_baseflow.hip", [], ""),
          ("lgar_leaf_tangent.hip", [], "")] + \
         [("lgar_kernels_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS] + \
-        [("lgar_tangent_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS] + \
-        [("lgar_tangent_window_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS]
-TANGENT_SOURCES = ("lgar_tangent_nl.hip", "lgar_tangent_window_nl.hip")  # what a build without the tangent leaves out
+        [("lgar_tangent_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS]
+TANGENT_SOURCES = ("lgar_tangent_nl.hip",)  # what a build without the tangent leaves out (both tangent kernel families)
 SOURCES = sorted(set(u[0] for u in UNITS))
 # every header the units may include (taken from the directory: a header left off a hand-kept list would let a stale library
 # be reused after it changed)
@@ -153,7 +152,7 @@ def build_variant(name, extra_flags, verbose=False, layers=(3,), tangent=False):
 
 def build(force=False, verbose=False):
     """Compile csrc/*.hip -> csrc/liblgar_hip.so.  hipcc cross-compiles gfx950 without a GPU.  The translation units
-    (C-ABI, probe, and one per soil-layer count for the forward, the tangent and the tangent-window kernels) are compiled concurrently into
+    (C-ABI, probe, and one per soil-layer count for the forward and for the tangent kernels) are compiled concurrently into
     csrc/obj/<fingerprint>/ and then linked.  Safe to call from several processes at once (file lock; the library is renamed
     into place)."""
     if not force and not _stale():

@@ -1,10 +1,9 @@
 // lgar_launch.hpp -- host-side launch entry points, one set per soil-layer count.
 //
 // The column physics is templated on the number of layers (per-layer parameters live in registers, loops over layers are
-// unrolled), so each layer count is its own translation unit: lgar_kernels_nl.hip / lgar_tangent_nl.hip /
-// lgar_tangent_window_nl.hip are compiled once
-// per NL of LGAR_LAYERS (lgar_plan.hpp) with -DLGAR_NL=<n> (lgar_py_amd/build.py), concurrently.  lgar_kernels.hip holds the
-// C-ABI and dispatches on dims->n_layers.
+// unrolled), so each layer count is its own translation unit: lgar_kernels_nl.hip (forward) and lgar_tangent_nl.hip (both
+// tangent kernel families) are compiled once per NL of LGAR_LAYERS (lgar_plan.hpp) with -DLGAR_NL=<n> (lgar_py_amd/build.py),
+// concurrently.  lgar_kernels.hip holds the C-ABI and dispatches on dims->n_layers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,7 +18,6 @@ template <int NL> int launch_forward_nl(const LgarDims *, const LgarParams *, Lg
 template <int NL> int launch_tangent_nl(const LgarDims *, const LgarParams *, const LgarParams *direction, const LgarForcing *,
                                         const void *w_runoff, const void *w_perc, void *grad_out, void *tangent_runoff,
                                         int32_t *status, int dtype, hipStream_t, unsigned *tickets);
-// (lgar_tangent_window_nl.hip)
 template <int NL> int launch_tangent_window_nl(const LgarDims *, const LgarParams *, const LgarParams *direction, const LgarForcing *,
                                                const void *w_runoff, const void *w_perc, const LgarTangentWindow *, void *grad_out,
                                                void *tangent_runoff, int32_t *status, int dtype, hipStream_t, unsigned *tickets);

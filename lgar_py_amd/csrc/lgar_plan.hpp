@@ -1,7 +1,8 @@
 // lgar_plan.hpp -- what one call launches, and with which arguments: the argument blocks of the kernels and the
 // front-capacity chain of a forward / tangent call.  Host-only and free of the HIP API, so the library's launchers
 // (lgar_kernels_nl.hip, lgar_tangent_nl.hip) and the test-only device-code simulator (tests/devsim, -DLGAR_DEVSIM) walk the
-// SAME plans with the SAME arguments; tests/test_launch_plan.py pins the plans themselves.
+// SAME plans with the SAME arguments; tests/test_launch_plan.py pins the plans themselves.  The tangent family's walk of its plan
+// is shared too: tangent_chain, beside the argument blocks it fills (lgar_tangent_body.hpp).
 #pragma once
 #include "lgar_forward_body.hpp"
 

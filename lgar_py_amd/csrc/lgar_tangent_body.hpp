@@ -10,11 +10,13 @@
 // column that could outgrow them is flagged LGAR_ST_RESUME and the second kernel (LGAR_FMAX slots) integrates exactly
 // those columns again from their fresh state (a tangent run always starts from set_internal_states).
 //
-// Window kernels (lgar_forward_tangent_window, lgar_tangent_window_nl.hip): tangent_lane<..., WINDOW = true> starts from a value
+// Window kernels (lgar_forward_tangent_window, lgar_tangent_window_kernel): tangent_lane<..., WINDOW = true> starts from a value
 // state + tangent state (TWindow::in / din) instead of the fresh one, continues the fold of grad from grad_in, and the kernel
 // that FINISHES a column stores both states (TWindow::out / dout).  A handed-over column is redone from in / din / grad_in, which
 // nobody writes.  Everything about the window sits behind `if constexpr (WINDOW)`: the plain instantiations are what they were.
 #pragma once
+#include <type_traits>
+
 #include "lgar_dual.hpp"
 #include "lgar_plan.hpp"
 
@@ -110,6 +112,29 @@ inline TWArgs<R> make_twargs(const LgarDims *d, const LgarParams *p, const LgarP
   t.w.dout = make_tstate<R, uint8_t, int32_t>(win->dstate_out);
   t.w.grad_in = (const R *)win->grad_in;
   return t;
+}
+
+// the TArgs of either argument block: what the launch and the chain write (ticket, chain_step)
+template <typename R> inline TArgs<R> &targs(TArgs<R> &a) { return a; }
+template <typename R> inline TArgs<R> &targs(TWArgs<R> &a) { return a.a; }
+
+// The walk of a tangent plan (lgar_plan.hpp), for both kernel families, the library's launcher and the host builds of the tests
+// alike: kernel i's place in the chain goes into the block, then run(cap, mode, work counter) -- cap and mode as
+// std::integral_constant -- runs kernel <CAP, MODE> on it and returns 0 or LGAR_E_*.  The first non-zero status ends the walk.
+template <typename A, typename Run> inline int tangent_chain(A &a, const TangentPlan &plan, unsigned *tickets, Run run) {
+  using Full = std::integral_constant<int, LGAR_FMAX>;
+  using Small = std::integral_constant<int, LGAR_CAP_SMALL>;
+  using Fast = std::integral_constant<int, MODE_FAST>;
+  using Literal = std::integral_constant<int, MODE_LITERAL>;
+  for (int i = 0; i < plan.n; i++) {
+    unsigned *tk = chain_step(targs(a), i, plan.n, tickets);
+    int rc;
+    if (plan.literal) rc = run(Full(), Literal(), tk);
+    else if (plan.caps[i] == LGAR_CAP_SMALL) rc = run(Small(), Fast(), tk);
+    else rc = run(Full(), Fast(), tk);
+    if (rc) return rc;
+  }
+  return 0;
 }
 
 template <typename R, int NL, int FMAX, int MODE, bool WINDOW = false>

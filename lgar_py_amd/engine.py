@@ -462,6 +462,20 @@ class LgarEngine:
                 raise LgarError("direction[%r] must be [L, N]" % k)
         return precip, pet, w_runoff, w_perc, dirs
 
+    def _tangent_call(self, name, inputs, forcing_map, want_series, window=(), grad=None, st=None):
+        """What tangent() and tangent_window() do alike with _tangent_inputs' results: lgar_<name> with the direction and forcing
+        blocks, `window` (the arguments between the weights and grad) and fresh work counters.  Returns (grad, series, st)."""
+        precip, pet, w_runoff, w_perc, dirs = inputs
+        dstruct = _capi.LgarParams(_ptr(dirs["alpha"]), _ptr(dirs["n"]), _ptr(dirs["ksat"]), None, None, None)
+        grad = torch.zeros(self.N, dtype=self.dtype, device=self.device) if grad is None else grad
+        ser = self._new_series(precip.shape[0], self.N, dtype=self.dtype, device=self.device) if want_series else None
+        st = torch.zeros(self.N, dtype=torch.int32, device=self.device) if st is None else st
+        tickets = torch.zeros(_capi.NTICKETS, dtype=torch.int32, device=self.device)  # persistent-wave work counters
+        fo = _capi.LgarForcing(precip.data_ptr(), pet.data_ptr(), None if forcing_map is None else forcing_map.index.data_ptr())
+        self._call(name, C.byref(self.dims), C.byref(self._params), C.byref(dstruct), C.byref(fo), _ptr(w_runoff), _ptr(w_perc),
+                   *window, grad.data_ptr(), _ptr(ser), st.data_ptr(), counters=tickets)
+        return grad, ser, st
+
     def tangent(self, direction, precip, pet, w_runoff=None, w_perc=None, want_series=False, forcing_group=1, share=0,
                 forcing_map=None):
         """Forward-mode tangent from a FRESH state (set_internal_states) over the whole forcing series.
@@ -477,18 +491,8 @@ class LgarEngine:
         Returns (grad[N], tangent_runoff[T, N] or None, status[N]) with
         grad[c] = sum_t w_runoff[t, c] * d runoff_t[c] + w_perc[t, c] * d percolation_t[c].  status != 0 marks columns whose
         tangent integration faulted (their grad entry is not a gradient): callers must check it (autograd.parameter_vjp does)."""
-        precip, pet, w_runoff, w_perc, dirs = self._tangent_inputs(direction, precip, pet, w_runoff, w_perc, forcing_group, share,
-                                                                   forcing_map)
-        T = precip.shape[0]
-        dstruct = _capi.LgarParams(_ptr(dirs["alpha"]), _ptr(dirs["n"]), _ptr(dirs["ksat"]), None, None, None)
-        grad = torch.zeros(self.N, dtype=self.dtype, device=self.device)
-        ser = self._new_series(T, self.N, dtype=self.dtype, device=self.device) if want_series else None
-        st = torch.zeros(self.N, dtype=torch.int32, device=self.device)
-        tickets = torch.zeros(_capi.NTICKETS, dtype=torch.int32, device=self.device)  # persistent-wave work counters
-        fo = _capi.LgarForcing(precip.data_ptr(), pet.data_ptr(), None if forcing_map is None else forcing_map.index.data_ptr())
-        self._call("forward_tangent", C.byref(self.dims), C.byref(self._params), C.byref(dstruct), C.byref(fo), _ptr(w_runoff),
-                   _ptr(w_perc), grad.data_ptr(), _ptr(ser), st.data_ptr(), counters=tickets)
-        return grad, ser, st
+        inputs = self._tangent_inputs(direction, precip, pet, w_runoff, w_perc, forcing_group, share, forcing_map)
+        return self._tangent_call("forward_tangent", inputs, forcing_map, want_series)
 
     def tangent_window(self, direction, precip, pet, w_runoff=None, w_perc=None, start=None, keep_state=True, want_series=False,
                        forcing_group=1, share=0, forcing_map=None):
@@ -504,9 +508,8 @@ class LgarEngine:
         state had faulted keep those fault bits in status.  This engine's own state is neither read nor written; an engine
         made with with_state=False will do.  The other arguments are tangent()'s; with share = W the W columns of a group
         must hold the same start values as well."""
-        precip, pet, w_runoff, w_perc, dirs = self._tangent_inputs(direction, precip, pet, w_runoff, w_perc, forcing_group, share,
-                                                                   forcing_map)
-        T, N = precip.shape[0], self.N
+        inputs = self._tangent_inputs(direction, precip, pet, w_runoff, w_perc, forcing_group, share, forcing_map)
+        N = self.N
         value = start.value if isinstance(start, TangentState) else start
         if value is not None:
             self._check_state(value, "start")
@@ -530,14 +533,8 @@ class LgarEngine:
         structs = [None if value is None else value._struct(), None if carried is None else carried._struct(),
                    None if end is None else end.value._struct(), None if end is None else end._struct()]
         win = _capi.LgarTangentWindow(*[None if s is None else C.addressof(s) for s in structs], None if carried is None else carried.grad.data_ptr())
-        dstruct = _capi.LgarParams(_ptr(dirs["alpha"]), _ptr(dirs["n"]), _ptr(dirs["ksat"]), None, None, None)
-        grad = z(N) if end is None else end.grad
-        ser = self._new_series(T, N, dtype=self.dtype, device=self.device) if want_series else None
-        st = z(N, dt=torch.int32) if end is None else end.value.status
-        tickets = z(_capi.NTICKETS, dt=torch.int32)
-        fo = _capi.LgarForcing(precip.data_ptr(), pet.data_ptr(), None if forcing_map is None else forcing_map.index.data_ptr())
-        self._call("forward_tangent_window", C.byref(self.dims), C.byref(self._params), C.byref(dstruct), C.byref(fo), _ptr(w_runoff),
-                   _ptr(w_perc), C.byref(win), grad.data_ptr(), _ptr(ser), st.data_ptr(), counters=tickets)
+        grad, ser, st = self._tangent_call("forward_tangent_window", inputs, forcing_map, want_series, (C.byref(win),),
+                                           *(() if end is None else (end.grad, end.value.status)))
         if value is not None:
             st |= value.status & _capi.ST_FAULT_MASK  # (the kernels write the status, they do not read it)
         return grad, ser, st, end

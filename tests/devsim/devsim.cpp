@@ -60,23 +60,16 @@ template <typename R, int NL> int init_typed(const LgarDims *d, const LgarParams
   return 0;
 }
 
-template <typename R, int NL, int CAP, int MODE> void run_tangent(const TArgs<R> &a) {
-  std::vector<WaveLDS<Dual<R>, CAP, 1>> lds(1);
-  for (int c = 0; c < a.N; c++) tangent_lane<R, NL, CAP, MODE>(&a, (size_t)c, 0, lds[0]);
-}
-
+// (the plan's walk is the library's own: tangent_chain, lgar_tangent_body.hpp)
 template <typename R, int NL>
 int tangent_typed(const LgarDims *d, const LgarParams *p, const LgarParams *dir, const LgarForcing *f, const void *wr, const void *wp,
                   void *grad, void *tser, int32_t *status) {
   TArgs<R> a = make_targs<R>(d, p, dir, f, wr, wp, grad, tser, status);
-  const TangentPlan plan = tangent_plan(d, NL);
-  for (int i = 0; i < plan.n; i++) {
-    chain_step(a, i, plan.n, nullptr);
-    if (plan.literal) run_tangent<R, NL, LGAR_FMAX, MODE_LITERAL>(a);
-    else if (plan.caps[i] == LGAR_CAP_SMALL) run_tangent<R, NL, LGAR_CAP_SMALL, MODE_FAST>(a);
-    else run_tangent<R, NL, LGAR_FMAX, MODE_FAST>(a);
-  }
-  return 0;
+  return tangent_chain(a, tangent_plan(d, NL), nullptr, [&](auto cap, auto mode, unsigned *) {
+    std::vector<WaveLDS<Dual<R>, decltype(cap)::value, 1>> lds(1);
+    for (int c = 0; c < a.N; c++) tangent_lane<R, NL, decltype(cap)::value, decltype(mode)::value>(&a, (size_t)c, 0, lds[0]);
+    return 0;
+  });
 }
 
 }  // namespace

@@ -1,8 +1,8 @@
 // window_host.cpp -- TEST INFRASTRUCTURE ONLY: the resumable tangent (lgar_forward_tangent_window) compiled for the host.
 //
-// The same headers the GPU kernels of lgar_py_amd/csrc/lgar_tangent_window_nl.hip are made of -- tangent_lane<..., WINDOW = true>,
-// make_twargs, tangent_plan, chain_step, the argument checks -- under -DLGAR_DEVSIM, one lane at a time, as tests/devsim does for
-// the entry points that existed before.  The product package never builds, loads or references this file.
+// The same headers the lgar_tangent_window_kernel family of lgar_py_amd/csrc/lgar_tangent_nl.hip is made of -- tangent_lane<...,
+// WINDOW = true>, make_twargs, tangent_plan, tangent_chain, the argument checks -- under -DLGAR_DEVSIM, one lane at a time, as
+// tests/devsim does for the entry points that existed before.  The product package never builds, loads or references this file.
 #define LGAR_DEVSIM 1
 #include <cmath>
 #include <cstdint>
@@ -21,23 +21,16 @@ using namespace lgar;
 
 namespace {
 
-template <typename R, int NL, int CAP, int MODE> void run_window(const TWArgs<R> &a) {
-  std::vector<WaveLDS<Dual<R>, CAP, 1>> lds(1);
-  for (int c = 0; c < a.a.N; c++) tangent_lane<R, NL, CAP, MODE, true>(&a.a, (size_t)c, 0, lds[0], nullptr, &a.w);
-}
-
 template <typename R, int NL>
 int window_typed(const LgarDims *d, const LgarParams *p, const LgarParams *dir, const LgarForcing *f, const void *wr, const void *wp,
                  const LgarTangentWindow *win, void *grad, void *tser, int32_t *status) {
   TWArgs<R> a = make_twargs<R>(d, p, dir, f, wr, wp, win, grad, tser, status);
-  const TangentPlan plan = tangent_plan(d, NL);
-  for (int i = 0; i < plan.n; i++) {
-    chain_step(a.a, i, plan.n, nullptr);
-    if (plan.literal) run_window<R, NL, LGAR_FMAX, MODE_LITERAL>(a);
-    else if (plan.caps[i] == LGAR_CAP_SMALL) run_window<R, NL, LGAR_CAP_SMALL, MODE_FAST>(a);
-    else run_window<R, NL, LGAR_FMAX, MODE_FAST>(a);
-  }
-  return 0;
+  return tangent_chain(a, tangent_plan(d, NL), nullptr, [&](auto cap, auto mode, unsigned *) {
+    std::vector<WaveLDS<Dual<R>, decltype(cap)::value, 1>> lds(1);
+    for (int c = 0; c < a.a.N; c++)
+      tangent_lane<R, NL, decltype(cap)::value, decltype(mode)::value, true>(&a.a, (size_t)c, 0, lds[0], nullptr, &a.w);
+    return 0;
+  });
 }
 
 }  // namespace
