@@ -473,6 +473,78 @@ int32_t lgar_network_route_grad(const double *gy, int32_t n_rows, int32_t n_catc
                                 const double *y, const int32_t *up_ptr, const int32_t *up_idx, int32_t n_edges,
                                 const double *state_in, double *gc, void *stream);
 
+/* Catchment network with flow-dependent reaches (Muskingum-Cunge): the storage constant of a reach is a power law of the reach's
+ * own previous discharge, K = kref (Oprev / qref)^(-beta), so a flood wave travels faster than low flow.  Everything is fp64,
+ * catchment fastest.  The topology, order, the HOST level_ptr, state_in / state_out [2][B] = Iprev, Oprev and the inflow fold are
+ * exactly lgar_network_route's.  par[4][B] = kref, beta, X, qref: kref the reach's travel time in hours at discharge qref, beta the
+ * celerity exponent, X the Muskingum weight, qref in the unit of x.  Scalars dt_h (the row step in hours), rmin, rmax (the range
+ * Oprev / qref is held to); half = 0.5 * dt_h, formed once.
+ *
+ * FORWARD.  For every reach b, with Iprev, Oprev = state_in[0][b], state_in[1][b] (NULL: +0.0), for t = 0 .. T - 1:
+ *     I   = x[t][b];  for e = up_ptr[b] .. up_ptr[b + 1] - 1:  I = I + y[t][up_idx[e]]      (the linear walk's own fold)
+ *     rho = Oprev / qref
+ *     rc  = rho < rmin ? rmin : (rho > rmax ? rmax : rho)       (selects: a NaN stays a NaN; rho == rmin / rmax is not "clamped")
+ *     L   = mc_ln(rc)
+ *     tau = beta * L                                            (K = kref * rc^(-beta))
+ *     ta  = tau < 0 ? -tau : tau;   tc = ta > LGAR_GW_ZMAX ? LGAR_GW_ZMAX : ta
+ *     e   = gw_exp(tc)                                          (lgar_catchment_baseflow's, as it is)
+ *     K   = tau > 0 ? kref / e : kref * e
+ *     KX  = K * X;   u = K - KX;   D = u + half
+ *     c0  = (half - KX) / D;   c1 = (half + KX) / D;   c2 = (u - half) / D
+ *     O   = (c0 * I + c1 * Iprev) + c2 * Oprev
+ *     y[t][b] = O;   Iprev = I;   Oprev = O
+ * in exactly this association, without contraction (-ffp-contract=off), with IEEE divisions.  state_out = Iprev, Oprev after the
+ * last row; y and state_out are WRITTEN, not added to; T = 0 copies the state (zeros when state_in is NULL); B = 0 is a no-op.  A
+ * negative or zero Oprev is simply rho < rmin.  Parameter VALUES are not policed on the device, and the coefficients may come
+ * out negative (they are non-negative iff 2 K X <= dt_h <= 2 K (1 - X)).  beta = 0 gives tau = 0, e = 1, K = kref exactly: the
+ * linear route with the Muskingum coefficients of (kref, X, dt_h), bit for bit.  Variable-K Muskingum does not conserve volume
+ * exactly in transients; a steady flow is kept (c0 + c1 + c2 = 1 up to rounding).
+ *
+ * mc_ln(x), x a positive normal double, uses no libm, no fma and no hardware reciprocal -- numpy restates it one operation for one:
+ *     (m, k) = frexp(x)                     by integer operations on the bits, m in [0.5, 1)
+ *     m < 0x1.6a09e667f3bcdp-1 ?            (fl(sqrt 1/2))   m = m + m, k = k - 1
+ *     s = (m - 1.0) / (m + 1.0);  z = s * s
+ *     p = sum_{j <= 10} z^j / (2 j + 1)     Horner from j = 10 down: p = p * z + c_j, one rounded multiply and one rounded add per
+ *                                           step, c_j the correctly rounded 1 / (2 j + 1)
+ *     L = k * LN2_HI + ((2.0 * s) * p + k * LN2_LO)          LN2_HI, LN2_LO: gw_exp's, so k * LN2_HI is exact
+ * Its relative error is below gamma_9 + 7e-19 = 1.0e-15 (derived in csrc/lgar_network_mc.hpp).
+ *
+ * Everything lgar_network_route refuses is refused here, and so are a dt_h that is not finite or <= 0, rmin or rmax that are not
+ * finite, rmin < 2^-60, rmax > 2^60, rmin > rmax and (B > 0) a null par: LGAR_E_ARG.  Indices read from device memory are clamped
+ * as in lgar_network_route; one launch per non-empty level on `stream`; offsets are 64-bit. */
+int32_t lgar_network_route_mc(const double *x, int32_t n_rows, int32_t n_catchments, const double *par, double dt_h, double rmin,
+                              double rmax, const int32_t *up_ptr, const int32_t *up_idx, int32_t n_edges, const int32_t *order,
+                              const int32_t *level_ptr, int32_t n_levels, const double *state_in, double *state_out, double *y,
+                              void *stream);
+
+/* The adjoint of the Muskingum-Cunge routing: from gy[T][B] the gradients with respect to x (gx[T][B]), to kref, beta and X
+ * (gpar[3][B] = gkref, gbeta, gX; NULL: not wanted; qref is a constant) and to the initial state (gstate[2][B]; NULL: not wanted).
+ * y is what lgar_network_route_mc stored for the same x, par, dt_h, rmin, rmax, state_in.  The levels run in DESCENDING order.
+ * I[t] is re-formed by the forward's fold; L, K, D, c0, c1, c2 and the regime of row t come from the forward's own row function
+ * with Oprev = y[t - 1][b] (row 0: state_in[1][b], or +0.0): the same bits.  inside = neither select of rc fired and not
+ * ta > LGAR_GW_ZMAX; big = ta > LGAR_GW_ZMAX.  Per reach, with omx = 1.0 - X (once), pI = pO = +0.0 and three accumulators from
+ * +0.0, for t = T - 1 .. 0, with Ip = I[t - 1], Op = y[t - 1][b] (row 0: state_in, or +0.0):
+ *     a     = gy[t][b];  if down[b] >= 0:  a = a + gx[t][down[b]]
+ *     lam   = a + pO
+ *     gx[t][b] = c0 * lam + pI
+ *     dK    = ((I * (-(X + c0 * omx)) + Ip * (X - c1 * omx)) + Op * (omx * (1.0 - c2))) / D;     GK = lam * dK
+ *     dX    = ((I * (-(1.0 - c0)) + Ip * (1.0 + c1)) + Op * (-(1.0 - c2))) * (K / D)
+ *     gkref = gkref + GK * (K / kref)
+ *     gbeta = big ? gbeta : gbeta + GK * (-(K * L))
+ *     gX    = gX + lam * dX
+ *     pI    = c1 * lam
+ *     pO    = inside ? c2 * lam + GK * ((-(beta * K)) / Op) : c2 * lam
+ * and gstate[0][b], gstate[1][b] = pI, pO after row 0.  In real arithmetic this is lam_t = a_t + c2_{t+1} lam_{t+1} +
+ * GK_{t+1} dK_{t+1}/dO_t and gx[t] = c0_t lam_t + c1_{t+1} lam_{t+1}, with dK/dOprev = -beta K / Oprev inside and 0 elsewhere.
+ * The regimes are selects on the forward's values, so a tie belongs where the forward sent it; every accumulator receives its
+ * terms in decreasing t, and one that receives no term in a row keeps its bits.  gx, gpar and gstate are WRITTEN; T = 0 writes
+ * zeros.  The refusals of lgar_network_route_mc, and (T > 0) a null gy, gx, x, y, down, up_ptr, or a null up_idx with
+ * n_edges > 0, return LGAR_E_ARG. */
+int32_t lgar_network_route_mc_grad(const double *gy, int32_t n_rows, int32_t n_catchments, const double *par, double dt_h, double rmin,
+                                   double rmax, const int32_t *down, const int32_t *order, const int32_t *level_ptr, int32_t n_levels,
+                                   double *gx, const double *x, const double *y, const int32_t *up_ptr, const int32_t *up_idx,
+                                   int32_t n_edges, const double *state_in, double *gpar, double *gstate, void *stream);
+
 /* Catchment baseflow: a groundwater store per catchment, fed by the catchment sums of percolation, that returns water to the
  * channel through the exponential storage-discharge relation (the nonlinear reservoir coupled below this infiltration scheme in
  * NextGen / CFE).  Its result is added to the routed runoff ahead of lgar_network_route.

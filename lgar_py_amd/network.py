@@ -6,9 +6,13 @@ one catchment; `downstream[b]` is the catchment b drains into, -1 for an outlet)
 levels and runs the kernels of csrc/lgar_network.hip (lgar_network_route / lgar_network_route_grad, include/lgar.h; DESIGN.md
 section 14 has the definition): one launch per level, the same bits whatever B, the launch or the run.  There is no CPU
 fallback: a network can be BUILT for device="cpu" (its host logic needs no GPU), every call needs the library and a GPU.
+route_mc / network_route_mc are the same walk with flow-dependent reaches (Muskingum-Cunge: K = kref (Oprev / qref)^(-beta),
+csrc/lgar_network_mc.hip, lgar_network_route_mc / lgar_network_route_mc_grad).
 
     autograd.lgar_series -> catchment_sum -> catchment_route -> network_route -> catchment_moments -> loss
 """
+import math
+
 import numpy as np
 import torch
 
@@ -29,6 +33,39 @@ def muskingum_coefficients(K_h, X, dt_h):
     half, KX = 0.5 * float(dt_h), K * X
     D = K - KX + half
     return torch.stack([(half - KX) / D, (half + KX) / D, (K - KX - half) / D])
+
+
+def manning_reach_parameters(length_m, slope, n_manning, width_m, qref_m3s):
+    """(kref_h, beta) of a reach for route_mc / network_route_mc from its geometry: the kinematic celerity of a wide rectangular
+    channel under Manning's formula is c(Q) = (5/3) n^(-3/5) S^(3/10) W^(-2/5) Q^(2/5), so the travel time length / c falls as
+    Q^(-2/5):
+        beta = 0.4,   kref = length / (3600 (5/3) n^(-3/5) slope^(3/10) width^(-2/5) qref^(2/5))      hours, at discharge qref
+    length_m and width_m in metres, slope dimensionless, qref_m3s in m^3/s: the discharge routed with these parameters must be in
+    m^3/s too (qref is handed to the routing in the unit of its x).  Plain differentiable torch in fp64; the arguments broadcast."""
+    f64 = lambda v: torch.as_tensor(v, dtype=torch.float64)
+    length = f64(length_m)
+    slope, n, width, qref = (f64(v).to(length.device) for v in (slope, n_manning, width_m, qref_m3s))
+    celerity = (5.0 / 3.0) * n ** -0.6 * slope ** 0.3 * width ** -0.4 * qref ** 0.4
+    kref = length / (3600.0 * celerity)
+    return kref, torch.full_like(kref, 0.4)
+
+
+MC_RMIN, MC_RMAX = 1.0 / 64.0, 64.0  # the default range Oprev / qref is held to
+_MC_RULES = (("kref", lambda v: v > 0.0, "> 0"), ("beta", lambda v: v >= 0.0, ">= 0"), ("X", lambda v: (v >= 0.0) & (v <= 0.5), "in 0 .. 0.5"),
+             ("qref", lambda v: v > 0.0, "> 0"))
+
+
+def _mc_scalars(dt_h, rmin, rmax):
+    """dt_h, rmin, rmax as floats; what lgar_network_route_mc would refuse raises here, with the reason."""
+    try:
+        dt, lo, hi = float(dt_h), float(rmin), float(rmax)
+    except (TypeError, ValueError) as err:
+        raise LgarError("dt_h, rmin, rmax must be numbers (%s)" % err)
+    if not math.isfinite(dt) or dt <= 0.0:
+        raise LgarError("dt_h must be finite and > 0 hours (got %r)" % (dt_h,))
+    if not (2.0 ** -60 <= lo <= hi <= 2.0 ** 60):
+        raise LgarError("rmin, rmax must satisfy 2^-60 <= rmin <= rmax <= 2^60 (got %r, %r)" % (rmin, rmax))
+    return dt, lo, hi
 
 
 class CatchmentNetwork:
@@ -95,6 +132,7 @@ class CatchmentNetwork:
         self.down, self.order, self.up_ptr, self.up_idx = (torch.from_numpy(a).to(self.device) for a in
                                                            (self.downstream_host, self.order_host, self.up_ptr_host, self.up_idx_host))
         self._states = {}  # key -> [2, B] carried state (absent: zeros)
+        self._mc_states = {}  # the same for route_mc: a key space of its own
 
     def upstream_of(self, b):
         """The direct upstream catchments of b, ascending (int32 array)."""
@@ -145,6 +183,49 @@ class CatchmentNetwork:
                      self.up_idx.data_ptr() if x is not None and self.n_edges else None, self.n_edges, ptr(state), ptr(gc))
         return gx, gc
 
+    def _mc_par(self, kref, beta, X, qref, validate):
+        """The fp64 [4, B] parameter block on the device from [B] tensors or scalars (broadcast).  validate: every value finite,
+        kref > 0, beta >= 0, 0 <= X <= 0.5, qref > 0, checked on the host."""
+        rows = []
+        for (name, ok, rule), v in zip(_MC_RULES, (kref, beta, X, qref)):
+            if not isinstance(v, torch.Tensor):
+                try:
+                    v = torch.tensor(float(v), dtype=torch.float64, device=self.device)
+                except (TypeError, ValueError) as err:
+                    raise LgarError("%s must be a fp64 [%d] tensor or a scalar (%s)" % (name, self.B, err))
+            if v.dtype != torch.float64 or v.device != self.order.device or v.dim() > 1 or (v.dim() == 1 and v.shape[0] != self.B):
+                raise LgarError("%s must be a fp64 [%d] tensor or a scalar on %s" % (name, self.B, self.device))
+            if validate:
+                host = v.detach().cpu().numpy().reshape(-1)
+                bad = np.nonzero(~(np.isfinite(host) & ok(host)))[0]
+                if bad.size:
+                    raise LgarError("%s[%d] = %r: every %s must be finite and %s" % (name, bad[0], float(host[bad[0]]), name, rule))
+            rows.append(v.detach().expand(self.B))
+        return torch.stack(rows).contiguous()
+
+    def _forward_mc(self, x, par, dt_h, rmin, rmax, state_in, want_state):
+        lib = self._open()
+        T = int(x.shape[0])
+        y = torch.empty(T, self.B, dtype=torch.float64, device=self.device)
+        state_out = torch.empty(2, self.B, dtype=torch.float64, device=self.device) if want_state else None
+        _capi.launch(lib, "network_route_mc", self.device, x.data_ptr(), T, self.B, par.data_ptr(), dt_h, rmin, rmax, self.up_ptr.data_ptr(),
+                     self.up_idx.data_ptr() if self.n_edges else None, self.n_edges, self.order.data_ptr(), self.level_ptr.ctypes.data,
+                     self.n_levels, ptr(state_in), ptr(state_out), y.data_ptr())
+        return y, state_out
+
+    def _backward_mc(self, gy, x, y, par, dt_h, rmin, rmax, state, want_par, want_state):
+        """(gx, gpar [3, B] or None, gstate [2, B] or None) of one lgar_network_route_mc_grad call."""
+        lib = self._open()
+        T = int(gy.shape[0])
+        gx = torch.empty(T, self.B, dtype=torch.float64, device=self.device)
+        gpar = torch.empty(3, self.B, dtype=torch.float64, device=self.device) if want_par else None
+        gstate = torch.empty(2, self.B, dtype=torch.float64, device=self.device) if want_state else None
+        _capi.launch(lib, "network_route_mc_grad", self.device, gy.data_ptr(), T, self.B, par.data_ptr(), dt_h, rmin, rmax,
+                     self.down.data_ptr(), self.order.data_ptr(), self.level_ptr.ctypes.data, self.n_levels, gx.data_ptr(), x.data_ptr(),
+                     y.data_ptr(), self.up_ptr.data_ptr(), self.up_idx.data_ptr() if self.n_edges else None, self.n_edges, ptr(state),
+                     ptr(gpar), ptr(gstate))
+        return gx, gpar, gstate
+
     # ------------------------------------------------------------------------------------------
     def route(self, x, coef, carry=True, key=None, state=None):
         """x: fp64 [T, B] lateral inflow (routed catchment runoff) on the network's device, coef: fp64 [3, B] (or [3]: all reaches
@@ -158,9 +239,32 @@ class CatchmentNetwork:
             return y
         return self._forward(x, coef, state, False)[0]
 
+    def route_mc(self, x, kref, beta, X, qref, dt_h, rmin=MC_RMIN, rmax=MC_RMAX, carry=True, key=None, state=None):
+        """route() with flow-dependent reaches (Muskingum-Cunge): in every row the storage constant of a reach is
+        K = kref (Oprev / qref)^(-beta), Oprev its own previous discharge held to rmin .. rmax times qref, and the row's Muskingum
+        coefficients are those of (K, X, dt_h).  kref (hours, the travel time at discharge qref), beta (the celerity exponent; 0.4
+        for Manning in a wide channel, manning_reach_parameters), X (the Muskingum weight) and qref (the unit of x): fp64 [B]
+        tensors on the network's device, or scalars that are broadcast.  Validated once per call, on the host: finite, kref > 0,
+        beta >= 0, 0 <= X <= 0.5, qref > 0, dt_h > 0, 2^-60 <= rmin <= rmax <= 2^60.  beta = 0 is route() with
+        muskingum_coefficients(kref, X, dt_h), bit for bit.  The coefficients of a row are non-negative iff
+        2 K X <= dt_h <= 2 K (1 - X) for that row's K; that is NOT enforced.  Variable-K Muskingum does not conserve volume
+        exactly in transients.  carry / key / state: as route(), in a key space of its own; chunked calls equal one call bit for
+        bit."""
+        dt_h, rmin, rmax = _mc_scalars(dt_h, rmin, rmax)
+        x, par, state = self._matrix(x, "x"), self._mc_par(kref, beta, X, qref, True), self._state(state)
+        if carry:
+            y, self._mc_states[key] = self._forward_mc(x, par, dt_h, rmin, rmax, self._mc_states.get(key) if state is None else state, True)
+            return y
+        return self._forward_mc(x, par, dt_h, rmin, rmax, state, False)[0]
+
+    def mc_state_of(self, key=None):
+        """The carried [2, B] state of route_mc's `key`, or None before the first carried call."""
+        return self._mc_states.get(key)
+
     def reset(self):
         """Forget every carried state."""
         self._states = {}
+        self._mc_states = {}
 
     def state_of(self, key=None):
         """The carried [2, B] state of `key` (row 0: the last inflow, row 1: the last discharge), or None before the first
@@ -218,3 +322,43 @@ def network_route(x, network, coef, state=None):
     if not isinstance(coef, torch.Tensor):
         raise LgarError("coef must be a fp64 [3, %d] tensor on %s" % (network.B, network.device))
     return _NetworkRoute.apply(x, coef, network, state)
+
+
+class _NetworkRouteMC(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, kref, beta, X, state, qref, network, dt_h, rmin, rmax):
+        xm = network._matrix(x, "x")
+        par = network._mc_par(kref, beta, X, qref, False)
+        st = network._state(state)
+        y = network._forward_mc(xm, par, dt_h, rmin, rmax, st, False)[0]
+        ctx.network, ctx.scalars, ctx.has_state = network, (dt_h, rmin, rmax), st is not None
+        ctx.scalar = tuple(not isinstance(p, torch.Tensor) or p.dim() == 0 for p in (kref, beta, X))
+        ctx.save_for_backward(xm, y, par, *(() if st is None else (st,)))
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xm, y, par = ctx.saved_tensors[:3]
+        st = ctx.saved_tensors[3] if ctx.has_state else None
+        net = ctx.network
+        gy = net._matrix(gy.contiguous(), "gy", int(xm.shape[0]))
+        want_state = ctx.has_state and ctx.needs_input_grad[4]
+        gx, gpar, gstate = net._backward_mc(gy, xm, y, par, *ctx.scalars, st, any(ctx.needs_input_grad[1:4]), want_state)
+        gp = [None, None, None]
+        for k in range(3):
+            if ctx.needs_input_grad[1 + k]:
+                gp[k] = gpar[k].sum() if ctx.scalar[k] else gpar[k]
+        return gx if ctx.needs_input_grad[0] else None, gp[0], gp[1], gp[2], gstate, None, None, None, None, None
+
+
+def network_route_mc(x, network, kref, beta, X, qref, dt_h, rmin=MC_RMIN, rmax=MC_RMAX, state=None):
+    """Differentiable network.route_mc(x, kref, beta, X, qref, dt_h): fp64 [T, B] -> [T, B].  x, kref, beta, X ([B] tensors, or
+    scalars: a scalar's gradient is summed over the reaches) and state ([2, B], the initial Iprev, Oprev; None: zeros) receive
+    gradients when they require one -- one backward launch sequence gives all of them; qref is a constant.  No stateful carry is
+    used or kept.  Parameter values are not validated here (route_mc validates; an optimiser keeps kref > 0, beta >= 0,
+    0 <= X <= 0.5 by its own transform): the kernels give the IEEE result for whatever they are handed.  The gradient is that of
+    the clamped statement: a reach whose Oprev / qref sits outside rmin .. rmax hands nothing back through K in that row."""
+    if not isinstance(network, CatchmentNetwork):
+        raise LgarError("network_route_mc takes a CatchmentNetwork")
+    dt_h, rmin, rmax = _mc_scalars(dt_h, rmin, rmax)
+    return _NetworkRouteMC.apply(x, kref, beta, X, state, qref, network, dt_h, rmin, rmax)
