@@ -545,6 +545,86 @@ int32_t lgar_network_route_mc_grad(const double *gy, int32_t n_rows, int32_t n_c
                                    double *gx, const double *x, const double *y, const int32_t *up_ptr, const int32_t *up_idx,
                                    int32_t n_edges, const double *state_in, double *gpar, double *gstate, void *stream);
 
+/* Catchment network with two node kinds: Muskingum-Cunge reaches (exactly lgar_network_route_mc's row) and level-pool reservoirs
+ * (lakes): a pool stores what arrives, releases by a power law of its active storage, never below its dead storage s0, and spills
+ * what does not fit below smax.  Everything is fp64, catchment fastest; the topology, the inflow fold, par_mc[4][B] (unread at a
+ * pool), dt_h, rmin, rmax are lgar_network_route_mc's.  The KIND of a node is given by its place in `order`: inside every level
+ * the reaches come first and the pools after them (each part by ascending index), and pool_ptr[n_levels] -- HOST memory, like
+ * level_ptr -- gives the split: positions level_ptr[l] .. pool_ptr[l] - 1 are reaches, pool_ptr[l] .. level_ptr[l + 1] - 1 pools,
+ * level_ptr[l] <= pool_ptr[l] <= level_ptr[l + 1].  A level gets up to two launches, one per kind; the order of the nodes inside
+ * a level never affects a bit.  The pool data are compact over the P = n_pools pools: pool_slot[B] (int32, device) = the pool's
+ * index 0 .. P - 1, -1 at a reach (clamped into 0 .. P - 1 when read at a pool); par_pool[5][P] = cq (the release at
+ * a = sref, in the unit of x), m (the exponent), s0 (dead storage), sref (> 0), smax (>= s0; +inf: never spills), storages in
+ * the unit of x times hours; storage[T][P] = S after every row (NULL: not wanted).  state_in / state_out [2][B] = (Iprev, Oprev)
+ * at a reach, (Iprev, S) at a pool.  prmin, prmax: the range a / sref is held to, 2^-60 <= prmin <= prmax <= 2^60.
+ *
+ * FORWARD at a pool b of slot s, with Iprev, S = state_in[0][b], state_in[1][b] (NULL: +0.0), half = 0.5 * dt_h and
+ * cap = smax - s0 formed once, for t = 0 .. T - 1:
+ *     I    = x[t][b];  for e = up_ptr[b] .. up_ptr[b + 1] - 1:  I = I + y[t][up_idx[e]]
+ *     vin  = half * (I + Iprev)
+ *     a    = S - s0;   rho = a / sref
+ *     lo   = rho < prmin;   hi = !lo && rho > prmax;   rc = lo ? prmin : (hi ? prmax : rho)
+ *     L    = mc_ln(rc);   tau = m * L
+ *     ta   = tau < 0 ? -tau : tau;   big = ta > LGAR_GW_ZMAX;   tc = big ? LGAR_GW_ZMAX : ta
+ *     e    = gw_exp(tc)
+ *     Ql   = tau > 0 ? cq * e : cq / e                        (the release law cq rc^m)
+ *     av   = a + vin;   qa = av / dt_h
+ *     free = Ql < qa;   Q = free ? Ql : qa                     (a NaN qa stays)
+ *     empty = Q < 0;    Q = empty ? 0.0 : Q                    (a NaN Q stays)
+ *     r    = av - dt_h * Q
+ *     ex   = r - cap;   spill = ex > 0
+ *     O    = spill ? Q + ex / dt_h : Q
+ *     S    = (spill ? cap : r) + s0
+ *     y[t][b] = O;   storage[t][s] = S;   Iprev = I
+ * in exactly this association, without contraction, with IEEE divisions; every decision is a select and ties go where the selects
+ * send them (rho == prmin / prmax is not clamped, Ql == qa is limited, ex == 0 does not spill).  m = 0 gives tau = 0, e = 1,
+ * Ql = cq exactly.  In real arithmetic S_t - S_(t-1) = vin_t - dt_h O_t in every regime: volume is conserved.  The explicit
+ * release can oscillate when cq dt_h is large against sref; that is not policed.  y, storage and state_out are WRITTEN; T = 0
+ * copies the state; B = 0 is a no-op; P = 0 is allowed (then par_pool, pool_slot and storage may be NULL and no level may have a
+ * pool segment) and is lgar_network_route_mc bit for bit.  |Ql - cq rc^m| <= (|tau| (1.0e-15 + u) + 4.56e-15 + u) cq rc^m for
+ * |tau| <= LGAR_GW_ZMAX (derived in csrc/lgar_network_pool.hpp).
+ *
+ * Refused with LGAR_E_ARG, the scalars first: everything lgar_network_route_mc refuses; prmin, prmax outside
+ * 2^-60 <= prmin <= prmax <= 2^60; n_pools < 0; a null pool_ptr with n_levels > 0; a pool_ptr[l] outside its level; a pool
+ * segment with n_pools = 0; with n_pools > 0 a null par_pool or pool_slot. */
+int32_t lgar_network_route_pool(const double *x, int32_t n_rows, int32_t n_catchments, const double *par_mc, const double *par_pool,
+                                int32_t n_pools, double dt_h, double rmin, double rmax, double prmin, double prmax,
+                                const int32_t *up_ptr, const int32_t *up_idx, int32_t n_edges, const int32_t *order,
+                                const int32_t *level_ptr, const int32_t *pool_ptr, int32_t n_levels, const int32_t *pool_slot,
+                                const double *state_in, double *state_out, double *y, double *storage, void *stream);
+
+/* The adjoint of lgar_network_route_pool: from gy[T][B] the gradients with respect to x (gx[T][B]), the reach parameters
+ * (gpar_mc[3][B], lgar_network_route_mc_grad's; +0.0 at a pool; NULL: not wanted), the pool parameters (gpool[4][P] = gcq, gm,
+ * gs0, gsmax; sref is a constant; NULL: not wanted) and the initial state (gstate[2][B]; NULL: not wanted).  y and storage are
+ * what the forward stored for the same arguments; storage is required when T > 0 and P > 0.  The levels run in DESCENDING order;
+ * gx[t][down[b]] is the adjoint of the downstream node's total inflow at either kind.  A reach runs lgar_network_route_mc_grad's
+ * rows.  A pool, with pI = pS = +0.0 and four accumulators from +0.0, for t = T - 1 .. 0, with Ip = I[t - 1],
+ * Sp = storage[t - 1][s] (row 0: state_in, or +0.0), the flags and a, L, e, Ql of the forward's row from S = Sp and
+ * vin = half * (I + Ip) (the same bits), inside = !lo && !hi && !big, and pw = tau > 0 ? e : 1.0 / e:
+ *     lamO  = gy[t][b];  if down[b] >= 0:  lamO = lamO + gx[t][down[b]]
+ *     lamS  = pS;   q = lamO / dt_h
+ *     gr    = spill ? q : lamS;   gcap = lamS - q                        (gcap is used where spill)
+ *     gQ    = empty ? 0.0 : lamO - dt_h * gr
+ *     gav   = free ? gr : gr + gQ / dt_h
+ *     ga    = free && inside ? gav + ((gQ * m) * Ql) / a : gav
+ *     gcq   = free ? gcq + gQ * pw : gcq
+ *     gm    = free && !big ? gm + (gQ * Ql) * L : gm
+ *     gs0   = (gs0 + (spill ? lamS - gcap : lamS)) - ga
+ *     gsmax = spill ? gsmax + gcap : gsmax
+ *     hg    = half * gav;   gx[t][b] = hg + pI;   pI = hg;   pS = ga
+ * and gstate[0][b], gstate[1][b] = pI, pS after row 0.  In real arithmetic: O = Q + (r - cap) / dt and S = smax where the pool
+ * spills, S = r + s0 elsewhere; r = av - dt Q; Q = Ql where free, av / dt where limited, 0 where empty; dQl/dcq = rc^m,
+ * dQl/dm = Ql ln rc unless big, dQl/da = m Ql / a inside; av = a + vin; a = S - s0.  The regimes are selects on the forward's own
+ * values, so a tie belongs where the forward sent it; an accumulator that receives no term in a row keeps its bits; inside is a
+ * select, not a multiply by zero.  Every output element is WRITTEN; T = 0 writes zeros.  Refused with LGAR_E_ARG: everything
+ * lgar_network_route_mc_grad and lgar_network_route_pool refuse, and a null storage with T > 0 and n_pools > 0. */
+int32_t lgar_network_route_pool_grad(const double *gy, int32_t n_rows, int32_t n_catchments, const double *par_mc, const double *par_pool,
+                                     int32_t n_pools, double dt_h, double rmin, double rmax, double prmin, double prmax,
+                                     const int32_t *down, const int32_t *order, const int32_t *level_ptr, const int32_t *pool_ptr,
+                                     int32_t n_levels, const int32_t *pool_slot, double *gx, const double *x, const double *y,
+                                     const double *storage, const int32_t *up_ptr, const int32_t *up_idx, int32_t n_edges,
+                                     const double *state_in, double *gpar_mc, double *gpool, double *gstate, void *stream);
+
 /* Catchment baseflow: a groundwater store per catchment, fed by the catchment sums of percolation, that returns water to the
  * channel through the exponential storage-discharge relation (the nonlinear reservoir coupled below this infiltration scheme in
  * NextGen / CFE).  Its result is added to the routed runoff ahead of lgar_network_route.

@@ -8,6 +8,8 @@ section 14 has the definition): one launch per level, the same bits whatever B, 
 fallback: a network can be BUILT for device="cpu" (its host logic needs no GPU), every call needs the library and a GPU.
 route_mc / network_route_mc are the same walk with flow-dependent reaches (Muskingum-Cunge: K = kref (Oprev / qref)^(-beta),
 csrc/lgar_network_mc.hip, lgar_network_route_mc / lgar_network_route_mc_grad).
+route_pool / network_route_pool add a second node kind, level-pool reservoirs at the nodes a NetworkPools names
+(csrc/lgar_network_pool.hip, lgar_network_route_pool / lgar_network_route_pool_grad).
 
     autograd.lgar_series -> catchment_sum -> catchment_route -> network_route -> catchment_moments -> loss
 """
@@ -50,7 +52,26 @@ def manning_reach_parameters(length_m, slope, n_manning, width_m, qref_m3s):
     return kref, torch.full_like(kref, 0.4)
 
 
+def weir_pool_parameters(area_m2, crest_length_m, weir_coefficient, href_m=1.0):
+    """(cq, m, sref) of a pool for route_pool / network_route_pool whose outlet is a free overfall (a weir of crest length L and
+    coefficient Cw, Q = Cw L h^1.5 in m^3/s with the head h in metres) and whose surface area does not change with the level, so
+    that the active storage is a = area h:
+        m = 1.5,   cq = Cw L href^1.5   (m^3/s, the release at head href),   sref = area href / 3600   (the storage at head href)
+    The routed discharge must be in m^3/s and the row step in hours, as for manning_reach_parameters: storages are then in
+    (m^3/s) h, which is why the area is divided by 3600.  s0 is the storage at the crest and smax the storage at which the pool
+    spills: both are the caller's.  Plain differentiable torch in fp64; the arguments broadcast."""
+    f64 = lambda v: torch.as_tensor(v, dtype=torch.float64)
+    area = f64(area_m2)
+    length, cw, href = (f64(v).to(area.device) for v in (crest_length_m, weir_coefficient, href_m))
+    area, length, cw, href = torch.broadcast_tensors(area, length, cw, href)
+    return cw * length * href ** 1.5, torch.full_like(area, 1.5), area * href / 3600.0
+
+
 MC_RMIN, MC_RMAX = 1.0 / 64.0, 64.0  # the default range Oprev / qref is held to
+POOL_RMIN, POOL_RMAX = 2.0 ** -20, 2.0 ** 20  # the default range (S - s0) / sref is held to
+_POOL_RULES = (("cq", lambda v, s0: np.isfinite(v) & (v >= 0.0), "finite and >= 0"), ("m", lambda v, s0: np.isfinite(v) & (v >= 0.0), "finite and >= 0"),
+               ("s0", lambda v, s0: np.isfinite(v), "finite"), ("sref", lambda v, s0: np.isfinite(v) & (v > 0.0), "finite and > 0"),
+               ("smax", lambda v, s0: v >= s0, ">= s0 (+inf: the pool never spills)"))
 _MC_RULES = (("kref", lambda v: v > 0.0, "> 0"), ("beta", lambda v: v >= 0.0, ">= 0"), ("X", lambda v: (v >= 0.0) & (v <= 0.5), "in 0 .. 0.5"),
              ("qref", lambda v: v > 0.0, "> 0"))
 
@@ -66,6 +87,18 @@ def _mc_scalars(dt_h, rmin, rmax):
     if not (2.0 ** -60 <= lo <= hi <= 2.0 ** 60):
         raise LgarError("rmin, rmax must satisfy 2^-60 <= rmin <= rmax <= 2^60 (got %r, %r)" % (rmin, rmax))
     return dt, lo, hi
+
+
+def _pool_scalars(dt_h, rmin, rmax, prmin, prmax):
+    """_mc_scalars and prmin, prmax as floats; what lgar_network_route_pool would refuse raises here, with the reason."""
+    dt, lo, hi = _mc_scalars(dt_h, rmin, rmax)
+    try:
+        plo, phi = float(prmin), float(prmax)
+    except (TypeError, ValueError) as err:
+        raise LgarError("prmin, prmax must be numbers (%s)" % err)
+    if not (2.0 ** -60 <= plo <= phi <= 2.0 ** 60):
+        raise LgarError("prmin, prmax must satisfy 2^-60 <= prmin <= prmax <= 2^60 (got %r, %r)" % (prmin, prmax))
+    return dt, lo, hi, plo, phi
 
 
 class CatchmentNetwork:
@@ -133,6 +166,7 @@ class CatchmentNetwork:
                                                            (self.downstream_host, self.order_host, self.up_ptr_host, self.up_idx_host))
         self._states = {}  # key -> [2, B] carried state (absent: zeros)
         self._mc_states = {}  # the same for route_mc: a key space of its own
+        self._pool_states = {}  # and for route_pool: (Iprev, Oprev) at a reach, (Iprev, S) at a pool
 
     def upstream_of(self, b):
         """The direct upstream catchments of b, ascending (int32 array)."""
@@ -226,6 +260,73 @@ class CatchmentNetwork:
                      ptr(gpar), ptr(gstate))
         return gx, gpar, gstate
 
+    def _pool_blocks(self, pools, reach, pool, validate):
+        """(par_mc [4, B], par_pool [5, P]) on the device from reach = (kref, beta, X, qref) ([B] tensors or scalars) and
+        pool = (cq, m, s0, sref, smax) ([P] tensors or scalars).  validate: on the host, and only where a value is read -- route_mc's
+        rules at the reaches; at the pools cq >= 0, m >= 0, sref > 0, smax >= s0, everything but smax finite."""
+        if not isinstance(pools, NetworkPools) or pools.network is not self:
+            raise LgarError("pools must be a NetworkPools of this network")
+        try:
+            kref, beta, X, qref = reach
+            values = tuple(pool)
+            assert len(values) == 5
+        except (TypeError, ValueError, AssertionError):
+            raise LgarError("reach must be (kref, beta, X, qref) and pool (cq, m, s0, sref, smax)")
+        par_mc = self._mc_par(kref, beta, X, qref, False)
+        rows = []
+        for (name, _, _), v in zip(_POOL_RULES, values):
+            if not isinstance(v, torch.Tensor):
+                try:
+                    v = torch.tensor(float(v), dtype=torch.float64, device=self.device)
+                except (TypeError, ValueError) as err:
+                    raise LgarError("%s must be a fp64 [%d] tensor or a scalar (%s)" % (name, pools.P, err))
+            if v.dtype != torch.float64 or v.device != self.order.device or v.dim() > 1 or (v.dim() == 1 and v.shape[0] != pools.P):
+                raise LgarError("%s must be a fp64 [%d] tensor or a scalar on %s" % (name, pools.P, self.device))
+            rows.append(v.detach().expand(pools.P))
+        par_pool = torch.stack(rows).contiguous()
+        if validate:
+            host = par_mc.cpu().numpy()
+            for (name, ok, rule), row in zip(_MC_RULES, host):
+                bad = np.nonzero(~(np.isfinite(row) & ok(row)) & ~pools.is_pool)[0]
+                if bad.size:
+                    raise LgarError("%s[%d] = %r: every %s of a reach must be finite and %s" % (name, bad[0], float(row[bad[0]]), name, rule))
+            host = par_pool.cpu().numpy()
+            for (name, ok, rule), row in zip(_POOL_RULES, host):
+                bad = np.nonzero(~ok(row, host[2]))[0]
+                if bad.size:
+                    raise LgarError("%s[%d] = %r (pool at catchment %d): every %s must be %s"
+                                    % (name, bad[0], float(row[bad[0]]), pools.nodes_host[bad[0]], name, rule))
+        return par_mc, par_pool
+
+    def _forward_pool(self, x, pools, par_mc, par_pool, scalars, state_in, want_state, want_storage):
+        """(y [T, B], state_out [2, B] or None, storage [T, P] or None) of one lgar_network_route_pool call; scalars = dt_h, rmin,
+        rmax, prmin, prmax."""
+        lib = self._open()
+        T, P = int(x.shape[0]), pools.P
+        y = torch.empty(T, self.B, dtype=torch.float64, device=self.device)
+        state_out = torch.empty(2, self.B, dtype=torch.float64, device=self.device) if want_state else None
+        storage = torch.empty(T, P, dtype=torch.float64, device=self.device) if want_storage else None
+        _capi.launch(lib, "network_route_pool", self.device, x.data_ptr(), T, self.B, par_mc.data_ptr(), par_pool.data_ptr() if P else None, P,
+                     *scalars, self.up_ptr.data_ptr(), self.up_idx.data_ptr() if self.n_edges else None, self.n_edges, pools.order.data_ptr(),
+                     self.level_ptr.ctypes.data, pools.pool_ptr.ctypes.data, self.n_levels, pools.pool_slot.data_ptr() if P else None,
+                     ptr(state_in), ptr(state_out), y.data_ptr(), storage.data_ptr() if want_storage and T and P else None)
+        return y, state_out, storage
+
+    def _backward_pool(self, gy, x, y, storage, pools, par_mc, par_pool, scalars, state, want_par, want_pool, want_state):
+        """(gx, gpar_mc [3, B] or None, gpool [4, P] or None, gstate [2, B] or None) of one lgar_network_route_pool_grad call."""
+        lib = self._open()
+        T, P = int(gy.shape[0]), pools.P
+        gx = torch.empty(T, self.B, dtype=torch.float64, device=self.device)
+        gpar = torch.empty(3, self.B, dtype=torch.float64, device=self.device) if want_par else None
+        gpool = torch.empty(4, P, dtype=torch.float64, device=self.device) if want_pool else None
+        gstate = torch.empty(2, self.B, dtype=torch.float64, device=self.device) if want_state else None
+        _capi.launch(lib, "network_route_pool_grad", self.device, gy.data_ptr(), T, self.B, par_mc.data_ptr(), par_pool.data_ptr() if P else None,
+                     P, *scalars, self.down.data_ptr(), pools.order.data_ptr(), self.level_ptr.ctypes.data, pools.pool_ptr.ctypes.data,
+                     self.n_levels, pools.pool_slot.data_ptr() if P else None, gx.data_ptr(), x.data_ptr(), y.data_ptr(),
+                     storage.data_ptr() if T and P else None, self.up_ptr.data_ptr(), self.up_idx.data_ptr() if self.n_edges else None,
+                     self.n_edges, ptr(state), ptr(gpar), gpool.data_ptr() if want_pool and P else None, ptr(gstate))
+        return gx, gpar, gpool, gstate
+
     # ------------------------------------------------------------------------------------------
     def route(self, x, coef, carry=True, key=None, state=None):
         """x: fp64 [T, B] lateral inflow (routed catchment runoff) on the network's device, coef: fp64 [3, B] (or [3]: all reaches
@@ -261,10 +362,41 @@ class CatchmentNetwork:
         """The carried [2, B] state of route_mc's `key`, or None before the first carried call."""
         return self._mc_states.get(key)
 
+    def route_pool(self, x, pools, reach, pool, dt_h, rmin=MC_RMIN, rmax=MC_RMAX, prmin=POOL_RMIN, prmax=POOL_RMAX, carry=True, key=None,
+                   state=None, return_storage=False):
+        """route_mc() on a network some of whose nodes are level-pool reservoirs (lakes).  pools: a NetworkPools of this network
+        (which nodes are pools); reach = (kref, beta, X, qref), route_mc's parameters, read at the reaches only; pool = (cq, m, s0,
+        sref, smax): fp64 [P] tensors on the network's device in the order of pools.nodes, or scalars that are broadcast.  A pool
+        with storage S holds the active storage a = S - s0 above its dead storage s0 and releases Ql = cq (a / sref)^m (a / sref held
+        to prmin .. prmax), at most what would drain it to s0 within the row and never less than zero; what does not fit below smax
+        spills in the same row (smax = +inf: never).  The volume in over a row is dt_h (I + Iprev) / 2 and the volume is conserved:
+        S_t - S_(t-1) = dt_h (I_t + I_(t-1)) / 2 - dt_h O_t.  Storages are in the unit of x times hours.  Validated once per call,
+        on the host, only where a value is read: route_mc's rules at the reaches; at the pools everything but smax finite,
+        cq >= 0, m >= 0, sref > 0, smax >= s0; dt_h > 0 and both ranges within 2^-60 .. 2^60.  The release is explicit (it is taken
+        at the storage the row starts from): where cq dt_h is large against sref the storage can overshoot its equilibrium and the
+        release oscillates from row to row.  That is NOT policed: choose dt_h below sref / (m cq) or so.  Without pools the result
+        is route_mc's, bit for bit.  carry / key / state: as route_mc(), in a key space of its own, the [2, B] state holding
+        (Iprev, Oprev) at a reach and (Iprev, S) at a pool; chunked calls equal one call bit for bit.  return_storage: also the
+        [T, P] storage series, (y, storage)."""
+        scalars = _pool_scalars(dt_h, rmin, rmax, prmin, prmax)
+        par_mc, par_pool = self._pool_blocks(pools, reach, pool, True)
+        x, state = self._matrix(x, "x"), self._state(state)
+        if carry:
+            y, self._pool_states[key], storage = self._forward_pool(x, pools, par_mc, par_pool, scalars,
+                                                                    self._pool_states.get(key) if state is None else state, True, return_storage)
+        else:
+            y, _, storage = self._forward_pool(x, pools, par_mc, par_pool, scalars, state, False, return_storage)
+        return (y, storage) if return_storage else y
+
+    def pool_state_of(self, key=None):
+        """The carried [2, B] state of route_pool's `key`, or None before the first carried call."""
+        return self._pool_states.get(key)
+
     def reset(self):
         """Forget every carried state."""
         self._states = {}
         self._mc_states = {}
+        self._pool_states = {}
 
     def state_of(self, key=None):
         """The carried [2, B] state of `key` (row 0: the last inflow, row 1: the last discharge), or None before the first
@@ -288,6 +420,47 @@ class CatchmentNetwork:
         gy = self._matrix(gy, "gy")
         T = int(gy.shape[0])
         return self._backward(gy, self._coef(coef), self._matrix(x, "x", T), self._matrix(y, "y", T), self._state(state))[1]
+
+
+class NetworkPools:
+    """Which nodes of a CatchmentNetwork are level-pool reservoirs.  nodes: [P] distinct catchment ids (P = 0 is allowed); pool
+    parameters and the storage series are in the order of `nodes`.  Validated once, on the host.  Builds what
+    lgar_network_route_pool needs without touching the network's own arrays: order = the catchments by (level, is_pool, index), so
+    that inside every level the reaches come first; pool_ptr[n_levels] (host) = where a level's pools start in that order;
+    pool_slot[B] (device) = the index of a pool in `nodes`, -1 at a reach."""
+
+    def __init__(self, network, nodes):
+        if not isinstance(network, CatchmentNetwork):
+            raise LgarError("NetworkPools takes a CatchmentNetwork")
+        try:
+            n = nodes.detach().cpu().numpy() if isinstance(nodes, torch.Tensor) else np.asarray(nodes)
+            if n.size == 0:
+                n = n.astype(np.int64)
+            if n.dtype.kind not in "iu":
+                raise TypeError("dtype %s" % n.dtype)
+            n = n.astype(np.int64)
+        except (TypeError, ValueError, RuntimeError) as err:
+            raise LgarError("nodes must be [P] integers, the catchments that are pools (%s)" % err)
+        if n.ndim != 1:
+            raise LgarError("nodes must be [P], one entry per pool (got shape %s)" % (tuple(n.shape),))
+        B = network.B
+        bad = np.nonzero((n < 0) | (n >= B))[0]
+        if bad.size:
+            raise LgarError("nodes[%d] = %d is no catchment: ids are 0 .. %d" % (bad[0], n[bad[0]], B - 1))
+        uniq, counts = np.unique(n, return_counts=True)
+        if (counts > 1).any():
+            raise LgarError("catchment %d is named twice in nodes: a pool is named once" % uniq[counts > 1][0])
+        self.network, self.P = network, int(n.shape[0])
+        self.nodes_host = n.astype(np.int32)
+        self.is_pool = np.zeros(B, dtype=bool)
+        self.is_pool[n] = True
+        level = network.levels.astype(np.int64)
+        self.order_host = np.lexsort((np.arange(B), self.is_pool, level)).astype(np.int32)
+        reaches = np.bincount(level[~self.is_pool], minlength=network.n_levels)
+        self.pool_ptr = np.ascontiguousarray(network.level_ptr[:network.n_levels] + reaches, dtype=np.int32)
+        self.pool_slot_host = np.full(B, -1, dtype=np.int32)
+        self.pool_slot_host[n] = np.arange(self.P, dtype=np.int32)
+        self.order, self.pool_slot = (torch.from_numpy(a).to(network.device) for a in (self.order_host, self.pool_slot_host))
 
 
 class _NetworkRoute(torch.autograd.Function):
@@ -362,3 +535,51 @@ def network_route_mc(x, network, kref, beta, X, qref, dt_h, rmin=MC_RMIN, rmax=M
         raise LgarError("network_route_mc takes a CatchmentNetwork")
     dt_h, rmin, rmax = _mc_scalars(dt_h, rmin, rmax)
     return _NetworkRouteMC.apply(x, kref, beta, X, state, qref, network, dt_h, rmin, rmax)
+
+
+class _NetworkRoutePool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, kref, beta, X, cq, m, s0, smax, state, qref, sref, network, pools, scalars):
+        xm = network._matrix(x, "x")
+        par_mc, par_pool = network._pool_blocks(pools, (kref, beta, X, qref), (cq, m, s0, sref, smax), False)
+        st = network._state(state)
+        y, _, storage = network._forward_pool(xm, pools, par_mc, par_pool, scalars, st, False, True)
+        ctx.network, ctx.pools, ctx.scalars, ctx.has_state = network, pools, scalars, st is not None
+        ctx.scalar = tuple(not isinstance(p, torch.Tensor) or p.dim() == 0 for p in (kref, beta, X, cq, m, s0, smax))
+        ctx.save_for_backward(xm, y, storage, par_mc, par_pool, *(() if st is None else (st,)))
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xm, y, storage, par_mc, par_pool = ctx.saved_tensors[:5]
+        st = ctx.saved_tensors[5] if ctx.has_state else None
+        net = ctx.network
+        gy = net._matrix(gy.contiguous(), "gy", int(xm.shape[0]))
+        want_state = ctx.has_state and ctx.needs_input_grad[8]
+        gx, gpar, gpool, gstate = net._backward_pool(gy, xm, y, storage, ctx.pools, par_mc, par_pool, ctx.scalars, st,
+                                                     any(ctx.needs_input_grad[1:4]), any(ctx.needs_input_grad[4:8]), want_state)
+        gp = [None] * 7
+        for k in range(7):
+            if ctx.needs_input_grad[1 + k]:
+                g = gpar[k] if k < 3 else gpool[k - 3]
+                gp[k] = g.sum() if ctx.scalar[k] else g
+        return (gx if ctx.needs_input_grad[0] else None, *gp, gstate, None, None, None, None, None)
+
+
+def network_route_pool(x, network, pools, reach, pool, dt_h, rmin=MC_RMIN, rmax=MC_RMAX, prmin=POOL_RMIN, prmax=POOL_RMAX, state=None):
+    """Differentiable network.route_pool(x, pools, reach, pool, dt_h): fp64 [T, B] -> [T, B].  x, kref, beta, X ([B] tensors or
+    scalars), cq, m, s0, smax ([P] tensors or scalars; a scalar's gradient is summed over the nodes it was broadcast to) and state
+    ([2, B]; None: zeros) receive gradients when they require one -- one backward launch sequence gives all of them; qref and sref
+    are constants.  A reach parameter receives +0.0 at a pool.  No stateful carry is used or kept.  Parameter values are not
+    validated here (route_pool validates).  The gradient is that of the clamped statement with its regimes held fixed: nothing
+    flows back through a release that the range, an empty pool or a spill has cut off.  The storage series is kept for the
+    backward pass but not returned: a loss on it is not supported (route_pool(return_storage=True) gives the series)."""
+    if not isinstance(network, CatchmentNetwork):
+        raise LgarError("network_route_pool takes a CatchmentNetwork")
+    scalars = _pool_scalars(dt_h, rmin, rmax, prmin, prmax)
+    try:
+        kref, beta, X, qref = reach
+        cq, m, s0, sref, smax = pool
+    except (TypeError, ValueError):
+        raise LgarError("reach must be (kref, beta, X, qref) and pool (cq, m, s0, sref, smax)")
+    return _NetworkRoutePool.apply(x, kref, beta, X, cq, m, s0, smax, state, qref, sref, network, pools, scalars)
