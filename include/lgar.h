@@ -686,6 +686,82 @@ int32_t lgar_catchment_baseflow_grad(const double *gq, const double *gs, const d
                                      int32_t n_catchments, const double *par, double dt_h, const double *state_in, double *gr,
                                      double *gpar, double *gstate, void *stream);
 
+/* Catchment snowpack: a temperature-index store per forcing cell AHEAD of the columns.  It takes precipitation and air
+ * temperature and hands on rain plus melt: w is the [T][B] water input lgar_forward reads as `precip` through a column map.
+ * Two states per cell, ice and held liquid water; a linear rain/snow transition, degree-day melt, refreezing of held liquid, a
+ * liquid holding capacity (the classic HBV / SNOW-17 family of routines).
+ *
+ * All arrays are fp64, cell fastest: the precipitation rate p[T][B] (the unit of the engine's forcing: depth per hour), the air
+ * temperature ta[T][B], the water input rate w[T][B], the pack ice[T][B], liq[T][B] (depth; both or neither: NULL = not wanted),
+ * par[7][B] = tlo, thi, tm, sfcf, cfmax, cfr, cwh (tlo, thi, tm: temperatures; sfcf: snowfall correction; cfmax: depth per degree
+ * per hour; cfr, cwh: fractions), state_in / state_out [2][B] = ice, liq; dt_h is the row step in hours.
+ *
+ * FORWARD.  For every cell b, with cd = cfmax[b] * dt_h, cr = cfr[b] * cd, span = thi[b] - tlo[b] (one rounding each, once) and
+ * (ice, liq) = state_in[.][b] (state_in == NULL: +0.0), for t = 0 .. T - 1:
+ *     Ta   = ta[t][b];   pd = p[t][b] * dt_h
+ *     lo   = Ta <= tlo;  hi = !lo && Ta >= thi
+ *     fr   = lo ? 0.0 : (hi ? 1.0 : (Ta - tlo) / span)                   (tlo == thi: the quotient is never selected)
+ *     rain = pd * fr;    dry = pd - rain;   snow = sfcf * dry
+ *     d    = Ta - tm;    warm = d > 0
+ *     ice1 = ice + snow
+ *     pm   = cd * d;     ml = pm > ice1
+ *     melt = warm ? (ml ? ice1 : pm) : 0.0
+ *     pr   = cr * (-d);  rl = pr > liq
+ *     refr = warm ? 0.0 : (rl ? liq : pr)
+ *     ice2 = (ice1 - melt) + refr
+ *     liq1 = ((liq + rain) + melt) - refr
+ *     cap  = cwh * ice2; over = liq1 > cap
+ *     out  = over ? liq1 - cap : 0.0
+ *     liq  = over ? cap : liq1;   ice = ice2
+ *     w[t][b] = out / dt_h;   ice[t][b] = ice;   liq[t][b] = liq
+ * in exactly this association, without contraction (-ffp-contract=off), IEEE divisions, no libm.  state_out = (ice, liq) after
+ * the last row (NULL: not wanted).  Every output is WRITTEN, not added to.  Every decision is a select, and ties go where the
+ * selects send them: Ta == tlo is lo, Ta == thi is hi, d == 0 is not warm, pm == ice1 melts pm, pr == liq refreezes pr,
+ * liq1 == cap holds.
+ *   Mass balance, in real arithmetic: ice_T + liq_T + dt_h sum w = ice_0 + liq_0 + dt_h sum (fr + sfcf (1 - fr)) p.
+ *   Empty store: T = 0 copies the state (zeros when state_in is NULL); B = 0 is a no-op.
+ *   Independence: the result for b is a pure function of column b of p, ta and par and of state_in[.][b].  A NaN fails every
+ *     comparison and takes the last alternative: a NaN in p[t][b] or ta[t][b] is in ice and liq of cell b from row t on and in no
+ *     other cell (out's last alternative is the constant 0.0: w of such a row is +0.0 -- the pack carries the NaN).
+ *   Warm identity: with a zero state, every Ta > max(thi, tm) and dt_h a power of two, w has the bits of p where p > 0 and is
+ *     +0.0 where p == 0.
+ * Refused with LGAR_E_ARG: negative sizes, a dt_h that is not finite or <= 0, exactly one of ice / liq given, a null pointer
+ * the sizes say will be read or written (T > 0: p, ta, par, w).  Parameter VALUES are not policed (a negative p, a negative
+ * initial liq, tlo > thi give the IEEE result).  One launch on `stream`; offsets are 64-bit. */
+int32_t lgar_catchment_snow(const double *p, const double *ta, int32_t n_rows, int32_t n_cells, const double *par, double dt_h,
+                            const double *state_in, double *state_out, double *w, double *ice, double *liq, void *stream);
+
+/* The adjoint of the snowpack: from gw[T][B], gice[T][B], gliq[T][B] (gice, gliq == NULL: zeros), the incoming gradients of w,
+ * ice and liq, the gradients with respect to p (gp[T][B]), to ta (gta[T][B]; NULL: not wanted), to the parameters (gpar[7][B] in
+ * par's order; NULL: not wanted) and to the initial state (gstate[2][B]; NULL: not wanted).  ice and liq are the pack the forward
+ * stored for the same p, ta, par, dt_h, state_in.  Row t is re-formed from ice[t - 1][b], liq[t - 1][b] (row 0: state_in, or
+ * +0.0) through the forward's own row function: every flag and value below has the forward's bits.  With li = ll = +0.0 and
+ * the accumulators gtlo, gthi, gtm, gsfcf, gcd, gcr, gcwh from +0.0, mid = !lo && !hi, for t = T - 1 .. 0:
+ *     li    = li + gice[t][b];   ll = ll + gliq[t][b];   go = gw[t][b] / dt_h
+ *     dl1   = over ? go : ll;    dcap = over ? ll - go : 0.0
+ *     di2   = li + cwh * dcap;   gcwh = over ? gcwh + dcap * ice2 : gcwh
+ *     dmelt = dl1 - di2;         drefr = di2 - dl1
+ *     wm = warm && ml;   wf = warm && !ml;   cl = !warm && rl;   cf = !warm && !rl
+ *     di1   = wm ? di2 + dmelt : di2;       dliq = cl ? dl1 + drefr : dl1
+ *     gcd   = wf ? gcd + dmelt * d : gcd;   gcr  = cf ? gcr + drefr * (-d) : gcr
+ *     gd    = wf ? dmelt * cd : (cf ? -(drefr * cr) : 0.0)
+ *     gtm   = wf || cf ? gtm - gd : gtm
+ *     gsfcf = gsfcf + di1 * dry
+ *     sd    = sfcf * di1;   drain = dl1 - sd;   dpd = sd + drain * fr;   dfr = drain * pd
+ *     gTa   = mid ? gd + dfr / span : gd
+ *     gtlo  = mid ? gtlo + (dfr * (Ta - thi)) / (span * span) : gtlo
+ *     gthi  = mid ? gthi - (dfr * (Ta - tlo)) / (span * span) : gthi
+ *     gp[t][b] = dpd * dt_h;   gta[t][b] = gTa;   li = di1;   ll = dliq
+ * and after row 0: gcfmax = dt_h * (gcd + cfr * gcr), gcfr = cd * gcr, gstate = (li, ll).  The regimes are selects on the
+ * forward's own values, so a tie belongs where the forward sent it; an accumulator that receives no term in a row keeps its bits
+ * (a select of the accumulator, not an added zero); a quotient by span is formed only inside a select that discards it outside
+ * mid.  Every output element is WRITTEN; T = 0 writes zeros.  Refused with LGAR_E_ARG: what lgar_catchment_snow refuses (T > 0:
+ * gw, p, ta, par, gp), and a null ice / liq with T > 0. */
+int32_t lgar_catchment_snow_grad(const double *gw, const double *gice, const double *gliq, const double *p, const double *ta,
+                                 const double *ice, const double *liq, int32_t n_rows, int32_t n_cells, const double *par,
+                                 double dt_h, const double *state_in, double *gp, double *gta, double *gpar, double *gstate,
+                                 void *stream);
+
 /* Run totals of a run cut into several lgar_forward calls.  lgar_forward sums a call's accumulators step by step from zero
  * and adds that sum to LgarState.totals, so a chunked run adds several partial sums where one call adds one: the same numbers in
  * another order, equal to the last bits only.  This replays the one-call order over series the chunks stored: for every j < 7

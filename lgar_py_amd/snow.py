@@ -1,0 +1,210 @@
+"""Catchment snowpack: a temperature-index store per forcing cell AHEAD of the columns, with its adjoint and parameter gradients.
+
+Where winter precipitation falls as snow it lies for weeks and reaches the soil as melt.  CatchmentSnow holds the seven
+parameters of the classic temperature-index routine (tlo, thi: the linear rain / snow transition; tm, cfmax: degree-day melt;
+cfr: refreezing of held liquid; cwh: the liquid holding capacity; sfcf: the snowfall correction), validates them once on the
+host and runs the kernels of csrc/lgar_snow.hip (lgar_catchment_snow / lgar_catchment_snow_grad, include/lgar.h; DESIGN.md
+section 19 has the definition): one launch per call, the same bits whatever B, the launch or the run.  Its result is the [T, B]
+water input LgarEngine.forward(water, pet, forcing_map=...) takes in the place of precipitation; its pack series (ice + liq) is
+what a user scores against snow-water-equivalent records (scores.CatchmentScore).  There is no CPU fallback: a store can be BUILT
+for device="cpu" (its host logic needs no GPU), every call needs the library and a GPU.
+
+    precip, temp [T, B] -> catchment_snow -> water [T, B] -> LgarEngine.forward(water, pet, forcing_map=...) -> ...
+                                          \\-> ice + liq [T, B] -> catchment_moments(SWE observations) -> loss
+
+PET under snow is the caller's concern: the store does not touch it (for example pet * ((ice + liq) == 0) switches it off under
+a pack).  A forcing gradient THROUGH the columns does not exist yet: catchment_snow hands gradients on from its own outputs
+(water, ice, liq) to its inputs, and the columns give none with respect to their forcing, so a loss on runoff does not reach the
+snow parameters -- a loss on the pack series does.
+"""
+import numpy as np
+import torch
+
+from . import _capi
+from ._capi import LgarError, ptr
+from .baseflow import _matrix, _time_step
+
+PAR_NAMES = ("tlo", "thi", "tm", "sfcf", "cfmax", "cfr", "cwh")
+NPAR = len(PAR_NAMES)
+
+
+def _state(x, what, B, device):
+    if not isinstance(x, torch.Tensor) or tuple(x.shape) != (2, B) or x.dtype != torch.float64 or x.device != device:
+        raise LgarError("%s must be a fp64 [2, %d] tensor (ice, liq) on %s" % (what, B, device))
+    return x.detach().contiguous()
+
+
+def _forward(lib, device, p, ta, par, dt_h, state_in, want_state, want_pack):
+    """(w, ice or None, liq or None, state_out or None) of one lgar_catchment_snow call."""
+    T, B = int(p.shape[0]), int(p.shape[1])
+    w = torch.empty(T, B, dtype=torch.float64, device=device)
+    ice = torch.empty(T, B, dtype=torch.float64, device=device) if want_pack else None
+    liq = torch.empty(T, B, dtype=torch.float64, device=device) if want_pack else None
+    state_out = torch.empty(2, B, dtype=torch.float64, device=device) if want_state else None
+    _capi.launch(lib, "catchment_snow", device, p.data_ptr(), ta.data_ptr(), T, B, par.data_ptr(), dt_h, ptr(state_in), ptr(state_out),
+                 w.data_ptr(), ptr(ice), ptr(liq))
+    return w, ice, liq, state_out
+
+
+def _backward(lib, device, gw, gice, gliq, p, ta, ice, liq, par, dt_h, state_in, want_ta, want_par, want_state):
+    """(gp, gta or None, gpar or None, gstate or None) of one lgar_catchment_snow_grad call."""
+    T, B = int(p.shape[0]), int(p.shape[1])
+    gp = torch.empty(T, B, dtype=torch.float64, device=device)
+    gta = torch.empty(T, B, dtype=torch.float64, device=device) if want_ta else None
+    gpar = torch.empty(NPAR, B, dtype=torch.float64, device=device) if want_par else None
+    gstate = torch.empty(2, B, dtype=torch.float64, device=device) if want_state else None
+    _capi.launch(lib, "catchment_snow_grad", device, gw.data_ptr(), ptr(gice), ptr(gliq), p.data_ptr(), ta.data_ptr(), ptr(ice), ptr(liq),
+                 T, B, par.data_ptr(), dt_h, ptr(state_in), gp.data_ptr(), ptr(gta), ptr(gpar), ptr(gstate))
+    return gp, gta, gpar, gstate
+
+
+class CatchmentSnow:
+    """tlo, thi, tm, sfcf, cfmax, cfr, cwh: [B] tensors, sequences, or scalars with n_catchments= (all cells alike); dt_h: the row
+    step in hours.  Below tlo all precipitation is snow, above thi all is rain, linear between; snowfall is multiplied by sfcf;
+    cfmax (depth per degree per hour) melts ice above tm; cfr * cfmax refreezes held liquid below tm; the pack holds liquid up to
+    cwh * ice.  Validated once, on the host: every value finite, tlo <= thi, sfcf, cfmax, cfr, cwh >= 0, dt_h > 0; anything else
+    raises LgarError.  .par is the fp64 [7, B] parameter block on the device, .B the number of forcing cells."""
+
+    def __init__(self, tlo, thi, tm, sfcf, cfmax, cfr, cwh, dt_h, device="cuda:0", n_catchments=None):
+        self.dt_h = _time_step(dt_h)
+        cols = []
+        for name, v in zip(PAR_NAMES, (tlo, thi, tm, sfcf, cfmax, cfr, cwh)):
+            if isinstance(v, torch.Tensor):
+                if v.dtype != torch.float64:
+                    raise LgarError("%s must be fp64 (got %s)" % (name, v.dtype))
+                v = v.detach().cpu().numpy()
+            try:
+                v = np.asarray(v, dtype=np.float64)
+            except (TypeError, ValueError) as err:
+                raise LgarError("%s must be numbers (%s)" % (name, err))
+            if v.ndim > 1:
+                raise LgarError("%s must be a scalar or [B], one entry per cell (got shape %s)" % (name, tuple(v.shape)))
+            cols.append((name, v))
+        sizes = {int(v.shape[0]) for _, v in cols if v.ndim == 1}
+        if n_catchments is not None:
+            sizes.add(int(n_catchments))
+        if len(sizes) != 1:
+            raise LgarError("%s must agree on one number of cells: [B] each, or scalars with n_catchments= (got %s)"
+                            % (", ".join(PAR_NAMES), sorted(sizes) or "scalars only"))
+        B = sizes.pop()
+        if not 0 <= B < 2 ** 31:
+            raise LgarError("0 .. 2^31 - 1 cells (got %d)" % B)
+        par = np.stack([np.broadcast_to(v, (B,)) for _, v in cols]).astype(np.float64)
+        for k, name in enumerate(PAR_NAMES):
+            ok = np.isfinite(par[k]) & (par[k] >= 0.0 if k >= 3 else True)
+            bad = np.nonzero(~ok)[0]
+            if bad.size:
+                raise LgarError("%s[%d] = %r: every %s must be finite%s" % (name, bad[0], float(par[k][bad[0]]), name, " and >= 0" if k >= 3 else ""))
+        bad = np.nonzero(~(par[0] <= par[1]))[0]
+        if bad.size:
+            raise LgarError("tlo[%d] = %r > thi[%d] = %r: the transition needs tlo <= thi" % (bad[0], float(par[0][bad[0]]), bad[0], float(par[1][bad[0]])))
+        self.B = B
+        self.device = torch.device(device)
+        self.par = torch.from_numpy(np.ascontiguousarray(par)).to(self.device)
+        self._states = {}  # key -> [2, B] carried pack (absent: zeros)
+
+    # ------------------------------------------------------------------------------------------
+    @classmethod
+    def _open(cls, device):
+        """The library the store runs on (what the test suite's host build of the kernels replaces)."""
+        return _capi.open_library(device, "the catchment snowpack runs on a ROCm GPU: there is no CPU fallback (device %s)")
+
+    def run(self, precip, temp, carry=True, key=None, state=None, pack=False):
+        """precip, temp: fp64 [T, B] on the store's device (precipitation rate in the unit of the engine's forcing, air
+        temperature) -> fp64 [T, B] water input rate, or (water, ice, liq) with pack=True.  carry=True: the [2, B] pack stays on
+        the device between calls, as CatchmentBaseflow.run keeps its storage: chunked calls equal one call bit for bit (one state
+        per `key`); `state` (a [2, B] tensor: ice, liq) replaces the carried state first.  carry=False: starts from `state` (or
+        None = no pack) and keeps nothing."""
+        p = _matrix(precip, "precip", self.B, self.device)
+        ta = _matrix(temp, "temp", self.B, self.device, int(p.shape[0]))
+        state = None if state is None else _state(state, "state", self.B, self.device)
+        state_in = (self._states.get(key) if state is None else state) if carry else state
+        w, ice, liq, state_out = _forward(self._open(self.device), self.device, p, ta, self.par, self.dt_h, state_in, bool(carry), bool(pack))
+        if carry:
+            self._states[key] = state_out
+        return (w, ice, liq) if pack else w
+
+    def reset(self):
+        """Forget every carried state."""
+        self._states = {}
+
+    def state_of(self, key=None):
+        """The carried [2, B] pack (ice, liq) of `key`, or None before the first carried call."""
+        return self._states.get(key)
+
+    # ------------------------------------------------------------------------------------------
+    @classmethod
+    def function(cls, precip, temp, tlo, thi, tm, sfcf, cfmax, cfr, cwh, dt_h, state=None, return_pack=False):
+        """catchment_snow (below) on the library this class opens."""
+        if not isinstance(precip, torch.Tensor) or precip.dim() != 2 or precip.dtype != torch.float64:
+            raise LgarError("precip must be a fp64 [T, B] tensor")
+        B, device = int(precip.shape[1]), precip.device
+        if not isinstance(temp, torch.Tensor) or temp.shape != precip.shape or temp.dtype != torch.float64 or temp.device != device:
+            raise LgarError("temp must be a fp64 [%d, %d] tensor on %s" % (precip.shape[0], B, device))
+        pars = []
+        for name, v in zip(PAR_NAMES, (tlo, thi, tm, sfcf, cfmax, cfr, cwh)):
+            if not isinstance(v, torch.Tensor):
+                try:
+                    v = torch.tensor(float(v), dtype=torch.float64, device=device)
+                except (TypeError, ValueError) as err:
+                    raise LgarError("%s must be a fp64 [%d] tensor or a scalar (%s)" % (name, B, err))
+            if v.dtype != torch.float64 or v.device != device or v.dim() > 1 or (v.dim() == 1 and v.shape[0] != B):
+                raise LgarError("%s must be a fp64 [%d] tensor or a scalar on %s" % (name, B, device))
+            pars.append(v)
+        if state is not None:
+            _state(state, "state", B, device)
+        out = _CatchmentSnow.apply(precip, temp, *pars, state, _time_step(dt_h), bool(return_pack), cls)
+        return out if return_pack else out[0]
+
+
+class _CatchmentSnow(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, precip, temp, tlo, thi, tm, sfcf, cfmax, cfr, cwh, state, dt_h, return_pack, owner):
+        B, device = int(precip.shape[1]), precip.device
+        p = _matrix(precip, "precip", B, device)
+        ta = _matrix(temp, "temp", B, device, int(p.shape[0]))
+        pars = (tlo, thi, tm, sfcf, cfmax, cfr, cwh)
+        par = torch.stack([v.detach().expand(B) for v in pars]).contiguous()
+        st = None if state is None else state.detach().contiguous()
+        needs = any(ctx.needs_input_grad[:3 + NPAR])
+        w, ice, liq, _ = _forward(owner._open(device), device, p, ta, par, dt_h, st, False, return_pack or needs)
+        ctx.owner, ctx.dt_h, ctx.has_state, ctx.return_pack = owner, dt_h, state is not None, return_pack
+        ctx.scalar = tuple(v.dim() == 0 for v in pars)
+        if needs:
+            ctx.save_for_backward(p, ta, par, ice, liq, *(() if st is None else (st,)))
+        if return_pack:
+            return w, ice, liq
+        return (w,)
+
+    @staticmethod
+    def backward(ctx, gw, gice=None, gliq=None):
+        p, ta, par, ice, liq = ctx.saved_tensors[:5]
+        st = ctx.saved_tensors[5] if ctx.has_state else None
+        T, B, device = int(p.shape[0]), int(p.shape[1]), p.device
+        gw = _matrix(gw.contiguous(), "gw", B, device, T)
+        gice = _matrix(gice.contiguous(), "gice", B, device, T) if ctx.return_pack else None
+        gliq = _matrix(gliq.contiguous(), "gliq", B, device, T) if ctx.return_pack else None
+        need = ctx.needs_input_grad
+        want_par, want_state = any(need[2:2 + NPAR]), ctx.has_state and need[2 + NPAR]
+        gp, gta, gpar, gstate = _backward(ctx.owner._open(device), device, gw, gice, gliq, p, ta, ice, liq, par, ctx.dt_h, st, need[1],
+                                          want_par, want_state)
+        gs = [None] * NPAR
+        for k in range(NPAR):
+            if need[2 + k]:
+                gs[k] = gpar[k].sum() if ctx.scalar[k] else gpar[k]
+        return (gp if need[0] else None, gta, *gs, gstate, None, None, None)
+
+
+def catchment_snow(precip, temp, tlo, thi, tm, sfcf, cfmax, cfr, cwh, dt_h, state=None, return_pack=False):
+    """Differentiable temperature-index snowpack: precip, temp fp64 [T, B] -> water input [T, B], or (water, ice, liq) with
+    return_pack=True.  tlo, thi, tm, sfcf, cfmax, cfr, cwh: fp64 [B] tensors or scalars (a scalar's gradient is summed over the
+    cells); state: the initial pack, [2, B] = ice, liq (None: no pack).  precip, temp, each of the seven parameters and state
+    receive gradients when they require one -- one backward launch gives all of them.  No stateful carry is used or kept.
+    Parameter values are not validated here (CatchmentSnow validates once; an optimiser keeps tlo <= thi and the four
+    non-negative ones by its own transform): the kernels give the IEEE result for whatever they are handed.
+
+    PET under snow is the caller's concern, for example pet * ((ice + liq) == 0).  A forcing gradient through the columns does
+    not exist yet: the gradient of `water` is consumed here, but LgarEngine / lgar_series give none with respect to their
+    forcing, so calibrate the snow parameters on the pack series (CatchmentScore of ice + liq against snow-water-equivalent
+    records).  A lapse rate or elevation bands are a shift of `temp` per cell in torch: temp receives its gradient."""
+    return CatchmentSnow.function(precip, temp, tlo, thi, tm, sfcf, cfmax, cfr, cwh, dt_h, state, return_pack)
