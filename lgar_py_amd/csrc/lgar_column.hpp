@@ -95,14 +95,29 @@ template <typename S, int MODE> struct ModeTraits : ScalarKind<S> {
   // their column mass sums a register copy of the table, and the event scan added to it costs a lone wave more in selects than
   // the scan's own walk -- configs[1] 78.4 -> 81.8 ms, one column 43.3 -> 45.9 ms, measured.)
   static constexpr bool fused_walk = !literal && !coop;
+  // plain fp32 fast mode: a wave whose columns all hold a "top-layer table" (Column::top_table) takes the sweep, the walk after it
+  // and calc_dzdt with the table's shape resolved at compile time (sweep_top, mass_and_events_top, calc_dzdt's `fast`): the same
+  // leaf functions on the same operands in the same order, so the same bits as the generic step.  -DLGAR_NO_TOP_LAYER_STEP
+  // compiles the kernels without it.
+#ifndef LGAR_NO_TOP_LAYER_STEP
+  static constexpr bool top_step = K::plain_f32 && !literal;
+#else
+  static constexpr bool top_step = false;
+#endif
 };
 
 // ---------------------------------------------------------------------------------------------
 // one soil column
 // ---------------------------------------------------------------------------------------------
-template <typename S, int NL, int FMAX, int MODE> struct Column {
+// Column::top_table (kernels with the top-layer step only: an empty base everywhere else, so that the other kernels' Column is
+// the struct it was)
+template <bool ON> struct TopTableFlag { bool top_table = false; };
+template <> struct TopTableFlag<false> { static constexpr bool top_table = false; };
+
+template <typename S, int NL, int FMAX, int MODE> struct Column : TopTableFlag<ModeTraits<S, MODE>::top_step> {
   using R = real_t<S>;
   using M = ModeTraits<S, MODE>;
+  using TopTableFlag<M::top_step>::top_table;  // the front table is a top-layer table: see is_top_table
   static constexpr int POL = M::pol;  // (the leaf functions' policy argument, everywhere below)
   const ColParams<S, NL> &P;
   const LGAR_KARG Glob<R> *G;  // run-time constants, in the kernarg segment (re-pointed by the kernel's time loop)
@@ -213,6 +228,21 @@ template <typename S, int NL, int FMAX, int MODE> struct Column {
       if (F.layer(i) == k) { if (len == 0) lo = i; len++; }
   }
 
+  // Top-layer table: m = nf - NL >= 1 in-layer fronts of layer 0 (flag 0: tagged 0, no boundary front), then the boundary fronts
+  // of layers 0 .. NL-1 in order -- what a column holds while its wetting fronts are all still inside the top layer (three
+  // quarters of the bench's wave-steps hold it in all 64 lanes, profiles/EXPERIMENTS.md round 8).  The flags and nf change only in
+  // the event passes and in create_surficial_front, never in the sweep: the predicate is evaluated when the state is loaded and
+  // after those two (both rare), and costs nothing in a step without them.
+  __device__ __forceinline__ bool is_top_table() const {
+    const int m = nf - NL;
+    bool t = m >= 1;
+    for (int i = 0; i < nf; i++) {
+      const int f = F.flag(i);
+      t = t && (f == ((i < m) ? 0 : ((i - m) | LGAR_FLAG_BOTTOM)));
+    }
+    return t;
+  }
+
   // Cooperating lanes (one wave alone on its SIMD): every dependent LDS read is ~130 cycles nothing else covers, and the column
   // mass reads the front table row by row.  A table of at most SCAN fronts (the usual case) is fetched in ONE round trip
   // instead, and the sum runs on registers with the row index a compile-time constant: the same terms in the same order, so the
@@ -308,6 +338,41 @@ template <typename S, int NL, int FMAX, int MODE> struct Column {
         i++;
       }
       ls[j] = sum;
+    }
+    S tot = ls[NL - 1];
+#pragma unroll
+    for (int j = NL - 2; j >= 0; j--) tot = ls[j] + tot;
+    ev = e;
+    return tot;
+  }
+
+  // ... and the same walk over a top-layer table (is_top_table): fronts 0 .. m are layer 0's, front m its boundary front, then
+  // one boundary front per layer -- no tag is read, every front is read once.  The terms, the tests and their order are
+  // mass_and_events' on such a table (a boundary front is never "passed"; the domain's deepest front is tested against nothing).
+  __device__ __forceinline__ S mass_and_events_top(bool &ev) const {
+    const int m = nf - NL;
+    S ls[NL];
+    bool e = false;
+    const S base0 = S(R(0.0));
+    S sum = S(R(0.0));
+    S zi = F.Z(0), ti = F.TH(0);
+    for (int i = 0; i < m; i++) {
+      const S zn = F.Z(i + 1), tn = F.TH(i + 1);
+      e = e || (i + 1 < m && val(zi) > val(zn));
+      e = e || (val(ti) <= val(tn));
+      e = e || (val(zi) > val(P.cum[0]));
+      sum = sum + (zi - base0) * (ti - tn);
+      zi = zn; ti = tn;
+    }
+    e = e || (val(zi) > val(P.cum[0]));
+    sum = sum + (zi - base0) * ti;
+    ls[0] = sum;
+#pragma unroll
+    for (int j = 1; j < NL; j++) {
+      const S base = P.cum[j] - P.thick[j];
+      const S z = F.Z(m + j), t = F.TH(m + j);
+      if (j < NL - 1) e = e || (val(z) > val(P.cum[j]));
+      ls[j] = S(R(0.0)) + (z - base) * t;
     }
     S tot = ls[NL - 1];
 #pragma unroll
@@ -951,13 +1016,66 @@ template <typename S, int NL, int FMAX, int MODE> struct Column {
     if constexpr (K > 0) sweep_from<K - 1>(c);
   }
 
+  // The sweep over a top-layer table (is_top_table; every column of the wave holds one): what sweep_from does on such a table,
+  // front by front in the same order, with the table's shape known.  The deepest front of the domain does nothing (the table has
+  // more than NL fronts: no base case); the boundary fronts of layers NL-2 .. 0, each the one front of its layer or the last of
+  // layer 0, take the continuity branch; the m fronts above run through layer 0's closed form, of whose carried pre-sweep triple
+  // only theta is read.  No layer tag is read, no loop runs over layers, no search is compiled in.
+  template <int K> __device__ __forceinline__ void sweep_top_boundary(int i) {
+    const LayerK<S> lk = pick_static(P, K);
+    const bool fresh = same_bits(F.PS(i), F.PS(i + 1));
+    if (!fresh) {
+      S ap;
+      F.TH(i) = theta_from_h_ap<S, POL>(lk, F.PS(i + 1), ap);
+      F.PS(i) = F.PS(i + 1);
+    }
+    if constexpr (K > 0) sweep_top_boundary<K - 1>(i - 1);
+  }
+  __device__ __forceinline__ void sweep_top(const SweepCarry &c) {
+    const LayerK<S> lk = pick_static(P, 0);
+    const int m = c.nf0 - NL;
+    S on_th = F.TH(m);  // pre-sweep theta of front i + 1
+    sweep_top_boundary<NL - 2>(m + NL - 2);
+    for (int i = m - 1; i >= 0; i--) {
+      const S oc_z = F.Z(i), oc_th = F.TH(i);
+      if (feq(i, m)) {  // (value-equal to the layer's last front: the reference sends it down the continuity branch)
+        const bool fresh = same_bits(F.PS(i), F.PS(i + 1));
+        if (!fresh) {
+          S ap;
+          F.TH(i) = theta_from_h_ap<S, POL>(lk, F.PS(i + 1), ap);
+          F.PS(i) = F.PS(i + 1);
+        }
+      } else {
+        S prior_mass = oc_z * (oc_th - on_th);
+        if (i == c.fdd || feq(c.fdd, i)) prior_mass = prior_mass + (c.infiltration - (R(0.0) + c.aet));
+        S z = F.Z(i) + (F.DZ(i) * G->dt_h);
+        z = mn(z, P.cum[NL - 1]);
+        F.Z(i) = z;
+        const bool zero_dzdt = ab(val(F.DZ(i))) <= R(1e-8);
+        if (!zero_dzdt) {  // (flag 0: not a just-created boundary front)
+          S potential = dv<POL>(prior_mass, z) + F.TH(i + 1);
+          F.TH(i) = mn(lk.te, potential);
+        }
+        F.PS(i) = h_from_se<S, POL>(lk, se_from_theta(lk, F.TH(i)));
+      }
+      on_th = oc_th;
+    }
+  }
+
   __device__ __forceinline__ void move_sweep(S infiltration, S aet, S old_mass, int fdd) {
     SweepCarry c;
     c.i = nf - 1; c.nf0 = nf; c.fdd = fdd;
     c.infiltration = infiltration; c.aet = aet;
     c.on_z = c.on_th = c.on_ps = S(R(0.0));
     c.near_sat = 0u;
-    sweep_from<NL - 1>(c);
+    if constexpr (M::top_step) {
+      const bool fast = any_lane(!top_table) == 0ull;  // wave-uniform: every active column holds a top-layer table
+      LGAR_COUNT_TOP_STEP(fast)
+      if (fast) sweep_top(c);
+      else sweep_from<NL - 1>(c);
+    } else {
+      sweep_from<NL - 1>(c);
+    }
     near_sat_fronts = c.near_sat;
     if constexpr (!M::fused_walk) {
       check_column_mass(fdd, old_mass, infiltration, aet);  // after front 0 (Layer.py:1296-1305)
@@ -986,7 +1104,12 @@ template <typename S, int NL, int FMAX, int MODE> struct Column {
         }
       }
       if (__builtin_expect(literal, 0)) check_column_mass(fdd, old_mass, infiltration, aet);
-      post_mass = mass_and_events(post_event);
+      if constexpr (M::top_step) {  // (the sweep changes no flag: the same lanes, the same tables, the same answer)
+        if (any_lane(!top_table) == 0ull) post_mass = mass_and_events_top(post_event);
+        else post_mass = mass_and_events(post_event);
+      } else {
+        post_mass = mass_and_events(post_event);
+      }
       if (stepped) {
         const R err = ab(val(post_mass) - val(mass_timestep));
         if (__builtin_expect(ab(err - Tol<R>::mass) > Tol<R>::mass, 0)) {
@@ -1199,6 +1322,7 @@ template <typename S, int NL, int FMAX, int MODE> struct Column {
       // needs the reference's full pass -- and a column with a near-saturated boundary front (below), whose bit may no longer
       // sit at the front's index after a deletion
       if constexpr (!M::literal) { if (psi_rewritten || near_sat_fronts != 0u) update_psi(); }
+      if constexpr (M::top_step) top_table = is_top_table();  // (the passes delete fronts and change tags)
     } else if constexpr (!M::literal && M::f64) {
       // A layer's deepest front takes the psi of the front below and theta(psi) of its own layer (Layer.py:389-418); the
       // reference's update_psi then re-derives psi from that theta.  The round trip returns psi to ~eps / (alpha psi)^n
@@ -1413,7 +1537,90 @@ template <typename S, int NL, int FMAX, int MODE> struct Column {
     }
   }
 
+  // calc_dzdt of the kernels with the top-layer step (M::top_step: plain fp32, one lane per column): the loop below with a
+  // wave-uniform `fast`.  Top-layer tables in every column of the wave (is_top_table): only the m = nf - NL fronts above the top
+  // layer's boundary front can move, all of them in layer 0 -- the scan reads no flag, the layer's parameters are layer 0's
+  // registers (no value-selects), the dz/dt formula is the top layer's, and the boundary fronts' dz/dt are zeroed after the
+  // loop.  The trapezoid's one call site and the wave-level loop serve both kinds of wave: every Geff, every dz/dt is the same.
+  // (A function of its own so that the other kernels' calc_dzdt stays the text -- and the instructions -- it was.)
+  __device__ __forceinline__ void calc_dzdt_top_step(S h_p) {
+    const bool fast = any_lane(!top_table) == 0ull;
+    const int m = nf - NL;
+    int i = -1;
+    for (;;) {
+      // advance to the next front that moves
+      bool found = false;
+      if (fast) {
+        while (!found && ++i < m) {
+          if (val(F.TH(i + 1)) > val(F.TH(i))) status |= LGAR_ST_THETA_ORDER;  // Layer.py:1206-1208
+          if (val(F.TH(i) - F.TH(i + 1)) > R(0.0)) found = true;
+          else F.DZ(i) = S(R(0.0));
+        }
+      } else {
+        while (!found && ++i < nf - 1) {
+          if (F.bottom(i)) { F.DZ(i) = S(R(0.0)); continue; }
+          const bool top = F.layer(i) == 0;
+          if (top && val(F.TH(i + 1)) > val(F.TH(i))) status |= LGAR_ST_THETA_ORDER;
+          if (val(F.TH(i) - F.TH(i + 1)) > R(0.0)) found = true;
+          else F.DZ(i) = S(R(0.0));
+        }
+      }
+      if (any_lane(found) == 0ull) break;
+      LGAR_MEASURE_POINT(CLK, 10)
+      if (found) {
+        int k = 0;
+        LayerK<S> lk;
+        if (fast) {
+          lk = pick_static(P, 0);
+        } else {
+          k = F.layer(i);
+          lk = pick(P, k);
+        }
+        S theta_1 = F.TH(i + 1), theta_2 = F.TH(i);
+        S delta_theta = F.TH(i) - F.TH(i + 1);
+        S g, ki;
+        bool fronts_done = false;
+        LGAR_MEASURE_POINT(F32_HEADS_FROM_PSI, lk, i, g, ki, fronts_done)
+        if (!fronts_done) {
+          g = capillary_drive(lk, theta_1, theta_2, 1);
+          ki = front_k(i, lk);
+#ifndef LGAR_NO_DZDT_MEMO
+          // (see calc_dzdt; a top-layer table's moving fronts are all in layer 0: the first of the layer is front 0)
+          if (same_bits(theta_2, lk.te) && (i == 0 || (!fast && F.layer(i - 1) != k))) { memo_theta = theta_1; memo_g = g; memo_layer = k; }
+#endif
+        }
+        if (is_nan(val(g))) status |= LGAR_ST_NAN;
+        S dzdt;
+        if (fast || k == 0) {
+          dzdt = dv<POL>(S(R(1.0)), delta_theta) * (dv<POL>(lk.ksat * (g + h_p), F.Z(i)) + ki);
+        } else {
+          S den = S(R(0.0)) + dv<POL>(F.Z(i) - cum_prev(k), ki);
+#pragma unroll
+          for (int j = 0; j < NL - 1; j++)
+            if (j < k) {
+              const LayerK<S> lj = pick_static(P, j);
+              S tl = theta_from_h<S, POL>(lj, F.PS(i));
+              S kl = k_from_se<S, POL>(lj, se_from_theta(lj, tl));
+              S pt = (j != 0) ? P.cum[(j > 0) ? j - 1 : 0] : S(R(0.0));
+              den = den + dv<POL>(P.cum[j] - pt, kl);
+            }
+          dzdt = dv<POL>(S(R(1.0)), delta_theta) * (dv<POL>(F.Z(i), den) + dv<POL>(lk.ksat * (g + h_p), F.Z(i)));
+        }
+        F.DZ(i) = dzdt;
+        LGAR_MEASURE_POINT(CLK, 17)
+      }
+    }
+    if (fast) {  // the boundary fronts but the domain's deepest (the generic scan zeroes them on its way)
+#pragma unroll
+      for (int j = 0; j < NL - 1; j++) F.DZ(m + j) = S(R(0.0));
+    }
+  }
+
   __device__ __forceinline__ void calc_dzdt(S h_p) {
+    if constexpr (M::top_step) {
+      calc_dzdt_top_step(h_p);
+      return;
+    }
     int i = -1;
     if constexpr (M::coop_f64 && M::mixed) {
       if (share_lanes >= 4 && !G->closed_form) i = calc_dzdt_pairs_mixed(h_p);
@@ -1726,6 +1933,7 @@ template <typename S, int NL, int FMAX, int MODE> struct Column {
         create_surficial_front(dry_depth, ponded_depth_sub, infiltration_sub);
         a_infil = a_infil + infiltration_sub;
         post_mass_valid = false;
+        if constexpr (M::top_step) top_table = is_top_table();  // (one more front, tagged as a boundary front if it fills the layer)
       }
       if (!inserting) {
         // update_ponded_depth, models/dpLGAR.py:369-382

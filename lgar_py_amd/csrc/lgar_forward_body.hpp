@@ -263,6 +263,7 @@ __device__ __forceinline__ void forward_lane(const LGAR_KARG KArgs<R> *ap, size_
   if (nf < NL) col.status |= LGAR_ST_STRUCT;  // not a state lgar_state_init / lgar_forward produced: column is skipped
   col.k_deepest = (nf > 0) ? a.k[(size_t)(nf - 1) * N + c] : R(0);
   col.new_front_frozen = false;
+  if constexpr (M::top_step) col.top_table = col.is_top_table();  // (kept up to date where the flags change: lgar_column.hpp)
   col.cap = FMAX < a.F ? FMAX : a.F;
   col.count_geff = a.counters != nullptr;
   col.share_lanes = (xchg != nullptr) ? a.coop : 0;

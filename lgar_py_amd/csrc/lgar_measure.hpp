@@ -15,6 +15,10 @@
 //   -DLGAR_NO_F32_RARE_GEFF    insert_water and calc_dry_depth inline their own copies of the fp32 trapezoid (no geff_f32_rare)
 //   -DLGAR_NO_GEFF_ENDS        the fp32 trapezoid's end nodes and its two heads as single dependent chains
 //   -DLGAR_NO_F32_REUSE        all three
+// ... and the one that compiles the plain fp32 kernels without the top-layer step (ModeTraits::top_step, lgar_column.hpp: every
+// wave takes the generic sweep and calc_dzdt; same bits; tests/test_devsim_top_layer_step.py, tests/test_gpu_top_layer_step.py):
+//   -DLGAR_NO_TOP_LAYER_STEP
+// -DLGAR_COUNT_TOP_LAYER_STEP=1|0 (lgar_scalar.hpp) counts the sub-steps that took it / did not, in the Geff counter's place.
 #pragma once
 #ifdef LGAR_NO_F32_REUSE
 #define LGAR_NO_DZDT_MEMO
@@ -72,8 +76,12 @@ __device__ __forceinline__ double opaque(double x) { asm volatile("" : "+v"(x));
 #else
 #define LGAR_COUNT_WHO (count_geff && first_active_lane())
 #endif
+#ifndef LGAR_COUNT_TOP_LAYER_STEP
 #define LGAR_COUNT_GEFF_CALL(site) \
   LGAR_COUNT_IF_SITE(site) LGAR_COUNT_IF_SPARSE { if (LGAR_COUNT_WHO) status += (1 << LGAR_ST_STEP_SHIFT); }
+#else
+#define LGAR_COUNT_GEFF_CALL(site)
+#endif
 #ifdef LGAR_DUP_GEFF
 #define LGAR_POINT_DUP_GEFF(lk, theta1, theta2)                                                    \
   if constexpr (!M::dual) {                                                                         \

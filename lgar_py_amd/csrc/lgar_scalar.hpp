@@ -173,8 +173,20 @@ __device__ __forceinline__ bool same_bits(float a, float b) { return a == b; }
 #define LGAR_ABLATABLE(NAME, ...) __VA_ARGS__
 // one lane per wave-level Geff evaluation adds 1 above the fault bits of its status word (no register, no LDS word; summed
 // over the wave at the end of the block): bits 8..31 are otherwise unused while a column is integrated
+#ifndef LGAR_COUNT_TOP_LAYER_STEP
 #define LGAR_COUNT_GEFF_CALL(site) \
   if (count_geff && first_active_lane()) status += (1 << LGAR_ST_STEP_SHIFT);
+#else
+#define LGAR_COUNT_GEFF_CALL(site)
+#endif
+#endif
+// -DLGAR_COUNT_TOP_LAYER_STEP=1 / =0 (tests only; the simulator's build can pass it too): the counter above counts the wave-level
+// sub-steps whose sweep took the top-layer step (1) or the generic one (0) INSTEAD of the Geff evaluations
+#ifdef LGAR_COUNT_TOP_LAYER_STEP
+#define LGAR_COUNT_TOP_STEP(fast) \
+  if (count_geff && first_active_lane() && (fast) == (LGAR_COUNT_TOP_LAYER_STEP != 0)) status += (1 << LGAR_ST_STEP_SHIFT);
+#else
+#define LGAR_COUNT_TOP_STEP(fast)
 #endif
 
 // tolerances: the reference's absolute 1e-12 (layers/Layer.py:60) is unreachable in fp32

@@ -34,12 +34,17 @@ run() {  # run NAME WORKLOAD rocprof-args...
   find /tmp/prof_$name \( -name "*counter_collection.csv" -o -name "*kernel_stats.csv" \) -size -20M -exec cp {} "$ROOT/$OUT/${wl}_$name/" \;
   rm -rf /tmp/prof_$name
 }
+# PASSES="stats valu" takes only those passes (default: all six)
 for wl in ${WORKLOADS:-f32 f64 tan mix}; do
   echo "workload $wl: $(date +%T)"
-  run stats $wl --stats
-  run valu $wl --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VALU_TRANS_F32 SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES
-  run mix $wl --pmc SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64
-  run wait $wl --pmc SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_SCA SQ_INSTS_BRANCH SQ_INSTS_VMEM SQ_LDS_BANK_CONFLICT SQ_WAVES GRBM_GUI_ACTIVE
-  run fetch $wl --pmc FETCH_SIZE GRBM_GUI_ACTIVE
-  run write $wl --pmc WRITE_SIZE
+  for pass in ${PASSES:-stats valu mix wait fetch write}; do
+    case $pass in
+      stats) run stats $wl --stats ;;
+      valu) run valu $wl --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VALU_TRANS_F32 SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES ;;
+      mix) run mix $wl --pmc SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 ;;
+      wait) run wait $wl --pmc SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_SCA SQ_INSTS_BRANCH SQ_INSTS_VMEM SQ_LDS_BANK_CONFLICT SQ_WAVES GRBM_GUI_ACTIVE ;;
+      fetch) run fetch $wl --pmc FETCH_SIZE GRBM_GUI_ACTIVE ;;
+      write) run write $wl --pmc WRITE_SIZE ;;
+    esac
+  done
 done
