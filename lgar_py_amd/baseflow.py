@@ -11,39 +11,15 @@ GPU), every call needs the library and a GPU.
     autograd.lgar_series -> catchment_sum -> catchment_route(runoff) + catchment_baseflow(percolation) -> network_route
         -> catchment_moments -> loss
 """
-import math
-
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, _stage
 from ._capi import LgarError, ptr
 
-
-def _time_step(dt_h):
-    try:
-        dt = float(dt_h)
-    except (TypeError, ValueError) as err:
-        raise LgarError("dt_h must be a number of hours (%s)" % err)
-    if not math.isfinite(dt) or dt <= 0.0:
-        raise LgarError("dt_h must be finite and > 0 hours (got %r)" % (dt_h,))
-    return dt
-
-
-def _matrix(x, what, B, device, rows=None):
-    """A fp64 [T, B] (rows=None) or [rows, B] tensor on `device`, detached and contiguous; anything else raises."""
-    if (not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] != B or x.dtype != torch.float64 or x.device != device
-            or (rows is not None and x.shape[0] != rows)):
-        raise LgarError("%s must be a fp64 [%s, %d] tensor on %s" % (what, "T" if rows is None else rows, B, device))
-    if x.shape[0] >= 2 ** 31:
-        raise LgarError("at most 2^31 - 1 rows")
-    return x.detach().contiguous()
-
-
-def _vector(x, what, B, device):
-    if not isinstance(x, torch.Tensor) or x.dim() != 1 or x.shape[0] != B or x.dtype != torch.float64 or x.device != device:
-        raise LgarError("%s must be a fp64 [%d] tensor on %s" % (what, B, device))
-    return x.detach().contiguous()
+PAR_NAMES = ("cgw", "expon", "smax")
+_RULES = (("cgw", lambda v, par: np.isfinite(v) & (v >= 0.0), "finite and >= 0"), ("expon", lambda v, par: np.isfinite(v) & (v > 0.0), "finite and > 0"),
+          ("smax", lambda v, par: np.isfinite(v) & (v > 0.0), "finite and > 0"))
 
 
 def _forward(lib, device, r, par, dt_h, state_in, want_state, want_storage):
@@ -75,35 +51,9 @@ class CatchmentBaseflow:
     else raises LgarError.  .par is the fp64 [3, B] parameter block on the device, .B the number of catchments."""
 
     def __init__(self, cgw, expon, smax, dt_h, device="cuda:0", n_catchments=None):
-        self.dt_h = _time_step(dt_h)
-        cols = []
-        for name, v in (("cgw", cgw), ("expon", expon), ("smax", smax)):
-            if isinstance(v, torch.Tensor):
-                if v.dtype != torch.float64:
-                    raise LgarError("%s must be fp64 (got %s)" % (name, v.dtype))
-                v = v.detach().cpu().numpy()
-            try:
-                v = np.asarray(v, dtype=np.float64)
-            except (TypeError, ValueError) as err:
-                raise LgarError("%s must be numbers (%s)" % (name, err))
-            if v.ndim > 1:
-                raise LgarError("%s must be a scalar or [B], one entry per catchment (got shape %s)" % (name, tuple(v.shape)))
-            cols.append((name, v))
-        sizes = {int(v.shape[0]) for _, v in cols if v.ndim == 1}
-        if n_catchments is not None:
-            sizes.add(int(n_catchments))
-        if len(sizes) != 1:
-            raise LgarError("cgw, expon, smax must agree on one number of catchments: [B] each, or scalars with n_catchments= (got %s)"
-                            % (sorted(sizes) or "scalars only",))
-        B = sizes.pop()
-        if not 0 <= B < 2 ** 31:
-            raise LgarError("0 .. 2^31 - 1 catchments (got %d)" % B)
-        par = np.stack([np.broadcast_to(v, (B,)) for _, v in cols]).astype(np.float64)
-        for k, (name, ok, rule) in enumerate((("cgw", par[0] >= 0.0, ">= 0"), ("expon", par[1] > 0.0, "> 0"), ("smax", par[2] > 0.0, "> 0"))):
-            bad = np.nonzero(~(np.isfinite(par[k]) & ok))[0]
-            if bad.size:
-                raise LgarError("%s[%d] = %r: every %s must be finite and %s" % (name, bad[0], float(par[k][bad[0]]), name, rule))
-        self.B = B
+        self.dt_h = _stage.time_step(dt_h)
+        par, self.B = _stage.block_on_host(PAR_NAMES, (cgw, expon, smax), n_catchments, "catchment")
+        _stage.check_rules(par, _RULES)
         self.device = torch.device(device)
         self.par = torch.from_numpy(np.ascontiguousarray(par)).to(self.device)
         self._states = {}  # key -> [B] carried storage (absent: zeros)
@@ -119,12 +69,10 @@ class CatchmentBaseflow:
         (baseflow, storage) with storage=True.  carry=True: the [B] storage stays on the device between calls, as
         CatchmentNetwork.route keeps its state: chunked calls equal one call bit for bit (one state per `key`); `state` (a [B]
         tensor) replaces the carried state first.  carry=False: starts from `state` (or None = zeros) and keeps nothing."""
-        r = _matrix(recharge, "recharge", self.B, self.device)
-        state = None if state is None else _vector(state, "state", self.B, self.device)
-        state_in = (self._states.get(key) if state is None else state) if carry else state
-        q, s, state_out = _forward(self._open(self.device), self.device, r, self.par, self.dt_h, state_in, bool(carry), bool(storage))
-        if carry:
-            self._states[key] = state_out
+        r = _stage.matrix(recharge, "recharge", self.B, self.device)
+        state = None if state is None else _stage.state_block(state, "state", (self.B,), self.device)
+        q, s, _ = _stage.carried(self._states, carry, key, state, lambda state_in, want_state: _forward(
+            self._open(self.device), self.device, r, self.par, self.dt_h, state_in, want_state, bool(storage)))
         return (q, s) if storage else q
 
     def reset(self):
@@ -142,19 +90,10 @@ class CatchmentBaseflow:
         if not isinstance(recharge, torch.Tensor) or recharge.dim() != 2 or recharge.dtype != torch.float64:
             raise LgarError("recharge must be a fp64 [T, B] tensor")
         B, device = int(recharge.shape[1]), recharge.device
-        pars = []
-        for name, v in (("cgw", cgw), ("expon", expon), ("smax", smax)):
-            if not isinstance(v, torch.Tensor):
-                try:
-                    v = torch.tensor(float(v), dtype=torch.float64, device=device)
-                except (TypeError, ValueError) as err:
-                    raise LgarError("%s must be a fp64 [%d] tensor or a scalar (%s)" % (name, B, err))
-            if v.dtype != torch.float64 or v.device != device or v.dim() > 1 or (v.dim() == 1 and v.shape[0] != B):
-                raise LgarError("%s must be a fp64 [%d] tensor or a scalar on %s" % (name, B, device))
-            pars.append(v)
+        pars = _stage.rows_on_device(PAR_NAMES, (cgw, expon, smax), B, device)
         if state is not None:
-            _vector(state, "state", B, device)
-        out = _CatchmentBaseflow.apply(recharge, pars[0], pars[1], pars[2], state, _time_step(dt_h), bool(return_storage), cls)
+            _stage.state_block(state, "state", (B,), device)
+        out = _CatchmentBaseflow.apply(recharge, *pars, state, _stage.time_step(dt_h), bool(return_storage), cls)
         return out if return_storage else out[0]
 
 
@@ -162,7 +101,7 @@ class _CatchmentBaseflow(torch.autograd.Function):
     @staticmethod
     def forward(ctx, recharge, cgw, expon, smax, state, dt_h, return_storage, owner):
         B, device = int(recharge.shape[1]), recharge.device
-        r = _matrix(recharge, "recharge", B, device)
+        r = _stage.matrix(recharge, "recharge", B, device)
         par = torch.stack([p.detach().expand(B) for p in (cgw, expon, smax)]).contiguous()
         st = None if state is None else state.detach().contiguous()
         needs = any(ctx.needs_input_grad[:5])
@@ -180,15 +119,12 @@ class _CatchmentBaseflow(torch.autograd.Function):
         r, par, s = ctx.saved_tensors[:3]
         st = ctx.saved_tensors[3] if ctx.has_state else None
         B, device = int(r.shape[1]), r.device
-        gq = _matrix(gq.contiguous(), "gq", B, device, int(r.shape[0]))
-        gs = _matrix(gs.contiguous(), "gs", B, device, int(r.shape[0])) if ctx.return_storage else None
+        gq = _stage.matrix(gq.contiguous(), "gq", B, device, int(r.shape[0]))
+        gs = _stage.matrix(gs.contiguous(), "gs", B, device, int(r.shape[0])) if ctx.return_storage else None
         want_par, want_state = any(ctx.needs_input_grad[1:4]), ctx.has_state and ctx.needs_input_grad[4]
         gr, gpar, gstate = _backward(ctx.owner._open(device), device, gq, gs, r, s, par, ctx.dt_h, st, want_par, want_state)
-        gp = [None, None, None]
-        for k in range(3):
-            if ctx.needs_input_grad[1 + k]:
-                gp[k] = gpar[k].sum() if ctx.scalar[k] else gpar[k]
-        return gr if ctx.needs_input_grad[0] else None, gp[0], gp[1], gp[2], gstate, None, None, None
+        gp = _stage.scalar_grads(gpar, ctx.needs_input_grad[1:4], ctx.scalar)
+        return gr if ctx.needs_input_grad[0] else None, *gp, gstate, None, None, None
 
 
 def catchment_baseflow(recharge, cgw, expon, smax, dt_h, state=None, return_storage=False):

@@ -13,12 +13,10 @@ route_pool / network_route_pool add a second node kind, level-pool reservoirs at
 
     autograd.lgar_series -> catchment_sum -> catchment_route -> network_route -> catchment_moments -> loss
 """
-import math
-
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, _stage
 from ._capi import LgarError, ptr
 
 
@@ -69,36 +67,28 @@ def weir_pool_parameters(area_m2, crest_length_m, weir_coefficient, href_m=1.0):
 
 MC_RMIN, MC_RMAX = 1.0 / 64.0, 64.0  # the default range Oprev / qref is held to
 POOL_RMIN, POOL_RMAX = 2.0 ** -20, 2.0 ** 20  # the default range (S - s0) / sref is held to
-_POOL_RULES = (("cq", lambda v, s0: np.isfinite(v) & (v >= 0.0), "finite and >= 0"), ("m", lambda v, s0: np.isfinite(v) & (v >= 0.0), "finite and >= 0"),
-               ("s0", lambda v, s0: np.isfinite(v), "finite"), ("sref", lambda v, s0: np.isfinite(v) & (v > 0.0), "finite and > 0"),
-               ("smax", lambda v, s0: v >= s0, ">= s0 (+inf: the pool never spills)"))
-_MC_RULES = (("kref", lambda v: v > 0.0, "> 0"), ("beta", lambda v: v >= 0.0, ">= 0"), ("X", lambda v: (v >= 0.0) & (v <= 0.5), "in 0 .. 0.5"),
-             ("qref", lambda v: v > 0.0, "> 0"))
+# (name, rule over (row, whole block), the rule in words) per row of a parameter block: _stage.check_rules
+_POOL_RULES = (("cq", lambda v, par: np.isfinite(v) & (v >= 0.0), "finite and >= 0"), ("m", lambda v, par: np.isfinite(v) & (v >= 0.0), "finite and >= 0"),
+               ("s0", lambda v, par: np.isfinite(v), "finite"), ("sref", lambda v, par: np.isfinite(v) & (v > 0.0), "finite and > 0"),
+               ("smax", lambda v, par: v >= par[2], ">= s0 (+inf: the pool never spills)"))
+_MC_RULES = (("kref", lambda v, par: np.isfinite(v) & (v > 0.0), "finite and > 0"), ("beta", lambda v, par: np.isfinite(v) & (v >= 0.0), "finite and >= 0"),
+             ("X", lambda v, par: np.isfinite(v) & (v >= 0.0) & (v <= 0.5), "finite and in 0 .. 0.5"),
+             ("qref", lambda v, par: np.isfinite(v) & (v > 0.0), "finite and > 0"))
+_MC_NAMES, _POOL_NAMES = tuple(r[0] for r in _MC_RULES), tuple(r[0] for r in _POOL_RULES)
 
 
 def _mc_scalars(dt_h, rmin, rmax):
     """dt_h, rmin, rmax as floats; what lgar_network_route_mc would refuse raises here, with the reason."""
     try:
-        dt, lo, hi = float(dt_h), float(rmin), float(rmax)
+        float(dt_h), float(rmin), float(rmax)
     except (TypeError, ValueError) as err:
         raise LgarError("dt_h, rmin, rmax must be numbers (%s)" % err)
-    if not math.isfinite(dt) or dt <= 0.0:
-        raise LgarError("dt_h must be finite and > 0 hours (got %r)" % (dt_h,))
-    if not (2.0 ** -60 <= lo <= hi <= 2.0 ** 60):
-        raise LgarError("rmin, rmax must satisfy 2^-60 <= rmin <= rmax <= 2^60 (got %r, %r)" % (rmin, rmax))
-    return dt, lo, hi
+    return (_stage.time_step(dt_h), *_stage.ratio_range(rmin, rmax, ("rmin", "rmax")))
 
 
 def _pool_scalars(dt_h, rmin, rmax, prmin, prmax):
     """_mc_scalars and prmin, prmax as floats; what lgar_network_route_pool would refuse raises here, with the reason."""
-    dt, lo, hi = _mc_scalars(dt_h, rmin, rmax)
-    try:
-        plo, phi = float(prmin), float(prmax)
-    except (TypeError, ValueError) as err:
-        raise LgarError("prmin, prmax must be numbers (%s)" % err)
-    if not (2.0 ** -60 <= plo <= phi <= 2.0 ** 60):
-        raise LgarError("prmin, prmax must satisfy 2^-60 <= prmin <= prmax <= 2^60 (got %r, %r)" % (prmin, prmax))
-    return dt, lo, hi, plo, phi
+    return (*_mc_scalars(dt_h, rmin, rmax), *_stage.ratio_range(prmin, prmax, ("prmin", "prmax")))
 
 
 class CatchmentNetwork:
@@ -180,12 +170,7 @@ class CatchmentNetwork:
         return _capi.open_library(self.device, "the catchment network runs on a ROCm GPU: there is no CPU fallback (network device %s)")
 
     def _matrix(self, x, what, rows=None):
-        if (not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] != self.B or x.dtype != torch.float64
-                or x.device != self.order.device or (rows is not None and x.shape[0] != rows)):
-            raise LgarError("%s must be a fp64 [%s, %d] tensor on %s" % (what, "T" if rows is None else rows, self.B, self.device))
-        if x.shape[0] >= 2 ** 31:
-            raise LgarError("at most 2^31 - 1 rows")
-        return x.detach().contiguous()
+        return _stage.matrix(x, what, self.B, self.order.device, rows, shown=self.device)
 
     def _coef(self, coef):
         if isinstance(coef, torch.Tensor) and coef.dim() == 1 and coef.shape[0] == 3:  # one reach's coefficients for all
@@ -221,21 +206,11 @@ class CatchmentNetwork:
         """The fp64 [4, B] parameter block on the device from [B] tensors or scalars (broadcast).  validate: every value finite,
         kref > 0, beta >= 0, 0 <= X <= 0.5, qref > 0, checked on the host."""
         rows = []
-        for (name, ok, rule), v in zip(_MC_RULES, (kref, beta, X, qref)):
-            if not isinstance(v, torch.Tensor):
-                try:
-                    v = torch.tensor(float(v), dtype=torch.float64, device=self.device)
-                except (TypeError, ValueError) as err:
-                    raise LgarError("%s must be a fp64 [%d] tensor or a scalar (%s)" % (name, self.B, err))
-            if v.dtype != torch.float64 or v.device != self.order.device or v.dim() > 1 or (v.dim() == 1 and v.shape[0] != self.B):
-                raise LgarError("%s must be a fp64 [%d] tensor or a scalar on %s" % (name, self.B, self.device))
+        for k, v in enumerate((kref, beta, X, qref)):  # (one by one: a bad value of kref is reported before a bad type of beta)
+            rows += _stage.rows_on_device(_MC_NAMES[k:k + 1], (v,), self.B, self.order.device, shown=self.device)
             if validate:
-                host = v.detach().cpu().numpy().reshape(-1)
-                bad = np.nonzero(~(np.isfinite(host) & ok(host)))[0]
-                if bad.size:
-                    raise LgarError("%s[%d] = %r: every %s must be finite and %s" % (name, bad[0], float(host[bad[0]]), name, rule))
-            rows.append(v.detach().expand(self.B))
-        return torch.stack(rows).contiguous()
+                _stage.check_rules(rows[k].detach().cpu().numpy().reshape(1, -1), _MC_RULES[k:k + 1])
+        return torch.stack([v.detach().expand(self.B) for v in rows]).contiguous()
 
     def _forward_mc(self, x, par, dt_h, rmin, rmax, state_in, want_state):
         lib = self._open()
@@ -273,29 +248,11 @@ class CatchmentNetwork:
         except (TypeError, ValueError, AssertionError):
             raise LgarError("reach must be (kref, beta, X, qref) and pool (cq, m, s0, sref, smax)")
         par_mc = self._mc_par(kref, beta, X, qref, False)
-        rows = []
-        for (name, _, _), v in zip(_POOL_RULES, values):
-            if not isinstance(v, torch.Tensor):
-                try:
-                    v = torch.tensor(float(v), dtype=torch.float64, device=self.device)
-                except (TypeError, ValueError) as err:
-                    raise LgarError("%s must be a fp64 [%d] tensor or a scalar (%s)" % (name, pools.P, err))
-            if v.dtype != torch.float64 or v.device != self.order.device or v.dim() > 1 or (v.dim() == 1 and v.shape[0] != pools.P):
-                raise LgarError("%s must be a fp64 [%d] tensor or a scalar on %s" % (name, pools.P, self.device))
-            rows.append(v.detach().expand(pools.P))
-        par_pool = torch.stack(rows).contiguous()
+        rows = _stage.rows_on_device(_POOL_NAMES, values, pools.P, self.order.device, shown=self.device)
+        par_pool = torch.stack([v.detach().expand(pools.P) for v in rows]).contiguous()
         if validate:
-            host = par_mc.cpu().numpy()
-            for (name, ok, rule), row in zip(_MC_RULES, host):
-                bad = np.nonzero(~(np.isfinite(row) & ok(row)) & ~pools.is_pool)[0]
-                if bad.size:
-                    raise LgarError("%s[%d] = %r: every %s of a reach must be finite and %s" % (name, bad[0], float(row[bad[0]]), name, rule))
-            host = par_pool.cpu().numpy()
-            for (name, ok, rule), row in zip(_POOL_RULES, host):
-                bad = np.nonzero(~ok(row, host[2]))[0]
-                if bad.size:
-                    raise LgarError("%s[%d] = %r (pool at catchment %d): every %s must be %s"
-                                    % (name, bad[0], float(row[bad[0]]), pools.nodes_host[bad[0]], name, rule))
+            _stage.check_rules(par_mc.cpu().numpy(), _MC_RULES, mask=~pools.is_pool, of=" of a reach")
+            _stage.check_rules(par_pool.cpu().numpy(), _POOL_RULES, where=lambda i: " (pool at catchment %d)" % pools.nodes_host[i])
         return par_mc, par_pool
 
     def _forward_pool(self, x, pools, par_mc, par_pool, scalars, state_in, want_state, want_storage):
@@ -335,10 +292,7 @@ class CatchmentNetwork:
         call bit for bit (one state per `key`); `state` (a [2, B] tensor) replaces the carried state first.  carry=False: starts
         from `state` (or None = zeros) and keeps nothing."""
         x, coef, state = self._matrix(x, "x"), self._coef(coef), self._state(state)
-        if carry:
-            y, self._states[key] = self._forward(x, coef, self._states.get(key) if state is None else state, True)
-            return y
-        return self._forward(x, coef, state, False)[0]
+        return _stage.carried(self._states, carry, key, state, lambda state_in, want_state: self._forward(x, coef, state_in, want_state))[0]
 
     def route_mc(self, x, kref, beta, X, qref, dt_h, rmin=MC_RMIN, rmax=MC_RMAX, carry=True, key=None, state=None):
         """route() with flow-dependent reaches (Muskingum-Cunge): in every row the storage constant of a reach is
@@ -353,10 +307,8 @@ class CatchmentNetwork:
         bit."""
         dt_h, rmin, rmax = _mc_scalars(dt_h, rmin, rmax)
         x, par, state = self._matrix(x, "x"), self._mc_par(kref, beta, X, qref, True), self._state(state)
-        if carry:
-            y, self._mc_states[key] = self._forward_mc(x, par, dt_h, rmin, rmax, self._mc_states.get(key) if state is None else state, True)
-            return y
-        return self._forward_mc(x, par, dt_h, rmin, rmax, state, False)[0]
+        return _stage.carried(self._mc_states, carry, key, state,
+                              lambda state_in, want_state: self._forward_mc(x, par, dt_h, rmin, rmax, state_in, want_state))[0]
 
     def mc_state_of(self, key=None):
         """The carried [2, B] state of route_mc's `key`, or None before the first carried call."""
@@ -381,11 +333,8 @@ class CatchmentNetwork:
         scalars = _pool_scalars(dt_h, rmin, rmax, prmin, prmax)
         par_mc, par_pool = self._pool_blocks(pools, reach, pool, True)
         x, state = self._matrix(x, "x"), self._state(state)
-        if carry:
-            y, self._pool_states[key], storage = self._forward_pool(x, pools, par_mc, par_pool, scalars,
-                                                                    self._pool_states.get(key) if state is None else state, True, return_storage)
-        else:
-            y, _, storage = self._forward_pool(x, pools, par_mc, par_pool, scalars, state, False, return_storage)
+        y, _, storage = _stage.carried(self._pool_states, carry, key, state, lambda state_in, want_state: self._forward_pool(
+            x, pools, par_mc, par_pool, scalars, state_in, want_state, return_storage), at=1)
         return (y, storage) if return_storage else y
 
     def pool_state_of(self, key=None):
@@ -517,11 +466,8 @@ class _NetworkRouteMC(torch.autograd.Function):
         gy = net._matrix(gy.contiguous(), "gy", int(xm.shape[0]))
         want_state = ctx.has_state and ctx.needs_input_grad[4]
         gx, gpar, gstate = net._backward_mc(gy, xm, y, par, *ctx.scalars, st, any(ctx.needs_input_grad[1:4]), want_state)
-        gp = [None, None, None]
-        for k in range(3):
-            if ctx.needs_input_grad[1 + k]:
-                gp[k] = gpar[k].sum() if ctx.scalar[k] else gpar[k]
-        return gx if ctx.needs_input_grad[0] else None, gp[0], gp[1], gp[2], gstate, None, None, None, None, None
+        gp = _stage.scalar_grads(gpar, ctx.needs_input_grad[1:4], ctx.scalar)
+        return gx if ctx.needs_input_grad[0] else None, *gp, gstate, None, None, None, None, None
 
 
 def network_route_mc(x, network, kref, beta, X, qref, dt_h, rmin=MC_RMIN, rmax=MC_RMAX, state=None):
@@ -558,12 +504,9 @@ class _NetworkRoutePool(torch.autograd.Function):
         want_state = ctx.has_state and ctx.needs_input_grad[8]
         gx, gpar, gpool, gstate = net._backward_pool(gy, xm, y, storage, ctx.pools, par_mc, par_pool, ctx.scalars, st,
                                                      any(ctx.needs_input_grad[1:4]), any(ctx.needs_input_grad[4:8]), want_state)
-        gp = [None] * 7
-        for k in range(7):
-            if ctx.needs_input_grad[1 + k]:
-                g = gpar[k] if k < 3 else gpool[k - 3]
-                gp[k] = g.sum() if ctx.scalar[k] else g
-        return (gx if ctx.needs_input_grad[0] else None, *gp, gstate, None, None, None, None, None)
+        need = ctx.needs_input_grad
+        gp = _stage.scalar_grads(gpar, need[1:4], ctx.scalar[:3]) + _stage.scalar_grads(gpool, need[4:8], ctx.scalar[3:])
+        return (gx if need[0] else None, *gp, gstate, None, None, None, None, None)
 
 
 def network_route_pool(x, network, pools, reach, pool, dt_h, rmin=MC_RMIN, rmax=MC_RMAX, prmin=POOL_RMIN, prmax=POOL_RMAX, state=None):

@@ -14,7 +14,7 @@ device="cpu" (its host logic needs no GPU), moments() and moments_grad() need th
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, _stage
 from ._capi import LgarError
 
 NMOM = _capi.SCORE_NMOM
@@ -66,10 +66,7 @@ class CatchmentScore:
         return sim.detach().contiguous()
 
     def _rows(self, x, rows, what):
-        if (not isinstance(x, torch.Tensor) or tuple(x.shape) != (rows, self.B) or x.dtype != torch.float64
-                or x.device != self.observations.device):
-            raise LgarError("%s must be a fp64 [%d, %d] tensor on %s" % (what, rows, self.B, self.device))
-        return x.detach().contiguous()
+        return _stage.matrix(x, what, self.B, self.observations.device, rows, shown=self.device)
 
     def _scratch(self, lib):
         """The device scratch of a call, kept on the object (the library allocates nothing)."""

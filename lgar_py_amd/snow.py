@@ -20,18 +20,17 @@ snow parameters -- a loss on the pack series does.
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, _stage
 from ._capi import LgarError, ptr
-from .baseflow import _matrix, _time_step
 
 PAR_NAMES = ("tlo", "thi", "tm", "sfcf", "cfmax", "cfr", "cwh")
 NPAR = len(PAR_NAMES)
+_RULES = tuple((name, lambda v, par: np.isfinite(v), "finite") if k < 3 else (name, lambda v, par: np.isfinite(v) & (v >= 0.0), "finite and >= 0")
+               for k, name in enumerate(PAR_NAMES))
 
 
 def _state(x, what, B, device):
-    if not isinstance(x, torch.Tensor) or tuple(x.shape) != (2, B) or x.dtype != torch.float64 or x.device != device:
-        raise LgarError("%s must be a fp64 [2, %d] tensor (ice, liq) on %s" % (what, B, device))
-    return x.detach().contiguous()
+    return _stage.state_block(x, what, (2, B), device, " (ice, liq)")
 
 
 def _forward(lib, device, p, ta, par, dt_h, state_in, want_state, want_pack):
@@ -66,39 +65,12 @@ class CatchmentSnow:
     raises LgarError.  .par is the fp64 [7, B] parameter block on the device, .B the number of forcing cells."""
 
     def __init__(self, tlo, thi, tm, sfcf, cfmax, cfr, cwh, dt_h, device="cuda:0", n_catchments=None):
-        self.dt_h = _time_step(dt_h)
-        cols = []
-        for name, v in zip(PAR_NAMES, (tlo, thi, tm, sfcf, cfmax, cfr, cwh)):
-            if isinstance(v, torch.Tensor):
-                if v.dtype != torch.float64:
-                    raise LgarError("%s must be fp64 (got %s)" % (name, v.dtype))
-                v = v.detach().cpu().numpy()
-            try:
-                v = np.asarray(v, dtype=np.float64)
-            except (TypeError, ValueError) as err:
-                raise LgarError("%s must be numbers (%s)" % (name, err))
-            if v.ndim > 1:
-                raise LgarError("%s must be a scalar or [B], one entry per cell (got shape %s)" % (name, tuple(v.shape)))
-            cols.append((name, v))
-        sizes = {int(v.shape[0]) for _, v in cols if v.ndim == 1}
-        if n_catchments is not None:
-            sizes.add(int(n_catchments))
-        if len(sizes) != 1:
-            raise LgarError("%s must agree on one number of cells: [B] each, or scalars with n_catchments= (got %s)"
-                            % (", ".join(PAR_NAMES), sorted(sizes) or "scalars only"))
-        B = sizes.pop()
-        if not 0 <= B < 2 ** 31:
-            raise LgarError("0 .. 2^31 - 1 cells (got %d)" % B)
-        par = np.stack([np.broadcast_to(v, (B,)) for _, v in cols]).astype(np.float64)
-        for k, name in enumerate(PAR_NAMES):
-            ok = np.isfinite(par[k]) & (par[k] >= 0.0 if k >= 3 else True)
-            bad = np.nonzero(~ok)[0]
-            if bad.size:
-                raise LgarError("%s[%d] = %r: every %s must be finite%s" % (name, bad[0], float(par[k][bad[0]]), name, " and >= 0" if k >= 3 else ""))
+        self.dt_h = _stage.time_step(dt_h)
+        par, self.B = _stage.block_on_host(PAR_NAMES, (tlo, thi, tm, sfcf, cfmax, cfr, cwh), n_catchments, "cell")
+        _stage.check_rules(par, _RULES)
         bad = np.nonzero(~(par[0] <= par[1]))[0]
         if bad.size:
             raise LgarError("tlo[%d] = %r > thi[%d] = %r: the transition needs tlo <= thi" % (bad[0], float(par[0][bad[0]]), bad[0], float(par[1][bad[0]])))
-        self.B = B
         self.device = torch.device(device)
         self.par = torch.from_numpy(np.ascontiguousarray(par)).to(self.device)
         self._states = {}  # key -> [2, B] carried pack (absent: zeros)
@@ -115,13 +87,11 @@ class CatchmentSnow:
         the device between calls, as CatchmentBaseflow.run keeps its storage: chunked calls equal one call bit for bit (one state
         per `key`); `state` (a [2, B] tensor: ice, liq) replaces the carried state first.  carry=False: starts from `state` (or
         None = no pack) and keeps nothing."""
-        p = _matrix(precip, "precip", self.B, self.device)
-        ta = _matrix(temp, "temp", self.B, self.device, int(p.shape[0]))
+        p = _stage.matrix(precip, "precip", self.B, self.device)
+        ta = _stage.matrix(temp, "temp", self.B, self.device, int(p.shape[0]))
         state = None if state is None else _state(state, "state", self.B, self.device)
-        state_in = (self._states.get(key) if state is None else state) if carry else state
-        w, ice, liq, state_out = _forward(self._open(self.device), self.device, p, ta, self.par, self.dt_h, state_in, bool(carry), bool(pack))
-        if carry:
-            self._states[key] = state_out
+        w, ice, liq, _ = _stage.carried(self._states, carry, key, state, lambda state_in, want_state: _forward(
+            self._open(self.device), self.device, p, ta, self.par, self.dt_h, state_in, want_state, bool(pack)))
         return (w, ice, liq) if pack else w
 
     def reset(self):
@@ -141,19 +111,10 @@ class CatchmentSnow:
         B, device = int(precip.shape[1]), precip.device
         if not isinstance(temp, torch.Tensor) or temp.shape != precip.shape or temp.dtype != torch.float64 or temp.device != device:
             raise LgarError("temp must be a fp64 [%d, %d] tensor on %s" % (precip.shape[0], B, device))
-        pars = []
-        for name, v in zip(PAR_NAMES, (tlo, thi, tm, sfcf, cfmax, cfr, cwh)):
-            if not isinstance(v, torch.Tensor):
-                try:
-                    v = torch.tensor(float(v), dtype=torch.float64, device=device)
-                except (TypeError, ValueError) as err:
-                    raise LgarError("%s must be a fp64 [%d] tensor or a scalar (%s)" % (name, B, err))
-            if v.dtype != torch.float64 or v.device != device or v.dim() > 1 or (v.dim() == 1 and v.shape[0] != B):
-                raise LgarError("%s must be a fp64 [%d] tensor or a scalar on %s" % (name, B, device))
-            pars.append(v)
+        pars = _stage.rows_on_device(PAR_NAMES, (tlo, thi, tm, sfcf, cfmax, cfr, cwh), B, device)
         if state is not None:
             _state(state, "state", B, device)
-        out = _CatchmentSnow.apply(precip, temp, *pars, state, _time_step(dt_h), bool(return_pack), cls)
+        out = _CatchmentSnow.apply(precip, temp, *pars, state, _stage.time_step(dt_h), bool(return_pack), cls)
         return out if return_pack else out[0]
 
 
@@ -161,8 +122,8 @@ class _CatchmentSnow(torch.autograd.Function):
     @staticmethod
     def forward(ctx, precip, temp, tlo, thi, tm, sfcf, cfmax, cfr, cwh, state, dt_h, return_pack, owner):
         B, device = int(precip.shape[1]), precip.device
-        p = _matrix(precip, "precip", B, device)
-        ta = _matrix(temp, "temp", B, device, int(p.shape[0]))
+        p = _stage.matrix(precip, "precip", B, device)
+        ta = _stage.matrix(temp, "temp", B, device, int(p.shape[0]))
         pars = (tlo, thi, tm, sfcf, cfmax, cfr, cwh)
         par = torch.stack([v.detach().expand(B) for v in pars]).contiguous()
         st = None if state is None else state.detach().contiguous()
@@ -181,17 +142,14 @@ class _CatchmentSnow(torch.autograd.Function):
         p, ta, par, ice, liq = ctx.saved_tensors[:5]
         st = ctx.saved_tensors[5] if ctx.has_state else None
         T, B, device = int(p.shape[0]), int(p.shape[1]), p.device
-        gw = _matrix(gw.contiguous(), "gw", B, device, T)
-        gice = _matrix(gice.contiguous(), "gice", B, device, T) if ctx.return_pack else None
-        gliq = _matrix(gliq.contiguous(), "gliq", B, device, T) if ctx.return_pack else None
+        gw = _stage.matrix(gw.contiguous(), "gw", B, device, T)
+        gice = _stage.matrix(gice.contiguous(), "gice", B, device, T) if ctx.return_pack else None
+        gliq = _stage.matrix(gliq.contiguous(), "gliq", B, device, T) if ctx.return_pack else None
         need = ctx.needs_input_grad
         want_par, want_state = any(need[2:2 + NPAR]), ctx.has_state and need[2 + NPAR]
         gp, gta, gpar, gstate = _backward(ctx.owner._open(device), device, gw, gice, gliq, p, ta, ice, liq, par, ctx.dt_h, st, need[1],
                                           want_par, want_state)
-        gs = [None] * NPAR
-        for k in range(NPAR):
-            if need[2 + k]:
-                gs[k] = gpar[k].sum() if ctx.scalar[k] else gpar[k]
+        gs = _stage.scalar_grads(gpar, need[2:2 + NPAR], ctx.scalar)
         return (gp if need[0] else None, gta, *gs, gstate, None, None, None)
 
 

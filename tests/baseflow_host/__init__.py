@@ -4,24 +4,22 @@ baseflow_host.cpp is the stand-alone program around them (run() below; also buil
 libbaseflowhost.so the same header as a shared library (library(): what SimCatchmentBaseflow puts behind the product's calling
 surface).  The numpy statement of the definition (include/lgar.h, lgar_catchment_baseflow / lgar_catchment_baseflow_grad;
 DESIGN.md section 15) -- gw_exp_ref, baseflow_ref, baseflow_grad_ref and regimes: plain loops over rows, the catchments side by
-side -- and the data of the tests' cases live here too.  Never imported by the product package.
+side -- and the data of the tests' cases live here too.
+The build, the program's call records (tests/_hostprog.hpp) and same_bits are tests/_hostbuild.py's: UNIT below.
+Never imported by the product package.
 """
 import ctypes as C
 import math
 import os
-import struct
-import tempfile
 from fractions import Fraction
 
 import numpy as np
 
 import _hostbuild
-from _hostbuild import CSRC, ROOT
+from _hostbuild import f64, out, same_bits  # noqa: F401
 from lgar_py_amd.baseflow import CatchmentBaseflow
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_HPP = os.path.join(_HERE, "baseflow_host.hpp")
-_DEPS = [os.path.join(CSRC, "lgar_baseflow.hpp"), os.path.join(ROOT, "include", "lgar.h")]
 SHAPE_B = (1, 2, 63, 64, 65, 257)
 SHAPE_T = (0, 1, 2, 7, 8, 9, 17)  # around the row chunk of 8
 
@@ -32,15 +30,6 @@ LN2_LO = float.fromhex("0x1.a39ef35793c76p-33")
 MAGIC = 1.5 * 2.0 ** 52
 COEF = [float(Fraction(1, math.factorial(j))) for j in range(14)]  # Fraction -> float rounds correctly
 ZERO, EMPTIED, FLUX = 0, 1, 2  # the regime of a row
-
-
-def same_bits(a, b):
-    """Bit-for-bit equality of two fp64 arrays (NaNs must sit in the same places)."""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.shape != b.shape or a.dtype != np.float64 or b.dtype != np.float64:
-        return False
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool((na == nb).all() and (a.view(np.uint64)[~na] == b.view(np.uint64)[~nb]).all())
 
 
 # ---- the definition, in numpy ----------------------------------------------------------------------------------------------
@@ -164,27 +153,14 @@ def case_data(rng, T, B):
 
 
 # ---- the host build --------------------------------------------------------------------------------------------------------
-def program(sanitize=False):
-    """The host program, built on first use with the ROCm clang (sanitize: AddressSanitizer + UBSan, any finding aborts)."""
-    return _hostbuild.build(os.path.join(_HERE, "baseflow_host_san" if sanitize else "baseflow_host"), os.path.join(_HERE, "baseflow_host.cpp"),
-                            [_HPP] + _DEPS, _hostbuild.SANITIZE if sanitize else [], "the catchment-baseflow host program")
-
-
-_lib = None
+UNIT = _hostbuild.HostUnit(_HERE, "baseflow_host", "baseflowhost", ["lgar_baseflow.hpp"], "catchment-baseflow")
 
 
 def library():
     """libbaseflowhost.so: baseflowhost_<entry point>(the arguments of include/lgar.h without the stream), loaded once."""
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(_hostbuild.build(os.path.join(_HERE, "libbaseflowhost.so"), _HPP, _DEPS, ["-fPIC", "-shared"],
-                                       "the catchment-baseflow host library"))
-        i32, vp, dbl = C.c_int32, C.c_void_p, C.c_double
-        _lib.baseflowhost_catchment_baseflow.argtypes = [vp, i32, i32, vp, dbl, vp, vp, vp, vp]
-        _lib.baseflowhost_catchment_baseflow_grad.argtypes = [vp, vp, vp, vp, i32, i32, vp, dbl, vp, vp, vp, vp]
-        _lib.baseflowhost_gw_exp.argtypes = [vp, i32, vp]
-        _lib.baseflowhost_gw_exp.restype = None
-    return _lib
+    i32, vp, dbl = C.c_int32, C.c_void_p, C.c_double
+    return UNIT.library({"catchment_baseflow": [vp, i32, i32, vp, dbl, vp, vp, vp, vp],
+                         "catchment_baseflow_grad": [vp, vp, vp, vp, i32, i32, vp, dbl, vp, vp, vp, vp], "gw_exp": [vp, i32, vp]}, {"gw_exp": None})
 
 
 def run(cases, sanitize=False):
@@ -192,57 +168,31 @@ def run(cases, sanitize=False):
     ("fwd", r, par, dt_h, state_in or None, want_s, want_state) gives (q, s or None, state_out or None);
     ("grad", gq, gs or None, r, s, par, dt_h, state_in or None, want_gpar, want_gstate) gives (gr, gpar or None, gstate or None);
     ("exp", z) gives (gw_exp(z),)."""
-    cases = list(cases)
-    blob, shapes = [struct.pack("i", len(cases))], []
-    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64).tobytes()
+    calls, results = [], []
     for case in cases:
         op = case[0]
         if op == "fwd":
             r, par, dt_h, state, want_s, want_state = case[1:]
             T, B = np.asarray(r).shape
             assert np.asarray(par).shape == (3, B)
-            blob += [struct.pack("8id", 0, T, B, state is not None, bool(want_s), bool(want_state), 0, 0, dt_h), f64(par), f64(r)]
-            blob += [f64(state)] if state is not None else []
-            shapes.append(((T, B), (T, B) if want_s else None, (B,) if want_state else None))
+            q, s, state_out = out(True, T, B), out(want_s, T, B), out(want_state, B)
+            calls.append((0, (T, B), (dt_h,), (f64(r), f64(par), f64(state), state_out, q, s)))
+            results.append((q, s, state_out))
         elif op == "grad":
             gq, gs, r, s, par, dt_h, state, want_par, want_state = case[1:]
             T, B = np.asarray(r).shape
             assert np.asarray(par).shape == (3, B) and np.asarray(s).shape == (T, B) and np.asarray(gq).shape == (T, B)
-            blob += [struct.pack("8id", 1, T, B, state is not None, gs is not None, bool(want_par), bool(want_state), 0, dt_h), f64(par), f64(gq)]
-            blob += ([f64(gs)] if gs is not None else []) + [f64(r), f64(s)] + ([f64(state)] if state is not None else [])
-            shapes.append(((T, B), (3, B) if want_par else None, (B,) if want_state else None))
+            gr, gpar, gstate = out(True, T, B), out(want_par, 3, B), out(want_state, B)
+            calls.append((1, (T, B), (dt_h,), (f64(gq), f64(gs), f64(r), f64(s), f64(par), f64(state), gr, gpar, gstate)))
+            results.append((gr, gpar, gstate))
         else:
             assert op == "exp"
             z = np.asarray(case[1], dtype=np.float64).ravel()
-            blob += [struct.pack("8id", 2, len(z), 0, 0, 0, 0, 0, 0, 1.0), f64(z)]
-            shapes.append(((len(z),),))
-    with tempfile.TemporaryDirectory() as tmp:
-        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
-        with open(fin, "wb") as fh:
-            fh.write(b"".join(blob))
-        _hostbuild.run_clean([program(sanitize), fin, fout])
-        raw = open(fout, "rb").read()
-    at, out = 0, []
-    for group in shapes:
-        got = []
-        for shape in group:
-            if shape is None:
-                got.append(None)
-                continue
-            n = int(np.prod(shape)) * 8
-            got.append(np.frombuffer(raw[at:at + n], dtype=np.float64).reshape(shape).copy())
-            at += n
-        out.append(tuple(got))
-    assert at == len(raw)
-    return out
-
-
-class _BaseflowLibrary:
-    """libbaseflowhost.so under the HIP library's names: lgar_<name>(arguments, stream) is baseflowhost_<name>(arguments)."""
-
-    def __getattr__(self, name):
-        fn = getattr(library(), "baseflowhost_" + name[len("lgar_"):])
-        return lambda *args: fn(*args[:-1])
+            e = out(True, len(z))
+            calls.append((2, (len(z),), (), (z, e)))
+            results.append((e,))
+    UNIT.run_calls(calls, sanitize)
+    return [_hostbuild.values(r) for r in results]
 
 
 class SimCatchmentBaseflow(CatchmentBaseflow):
@@ -254,4 +204,4 @@ class SimCatchmentBaseflow(CatchmentBaseflow):
 
     @classmethod
     def _open(cls, device):
-        return _BaseflowLibrary()
+        return _hostbuild.AsHipLibrary(("", "baseflowhost", library))

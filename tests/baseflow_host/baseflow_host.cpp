@@ -1,94 +1,21 @@
-// TEST INFRASTRUCTURE ONLY -- stand-alone host program around baseflow_host.hpp.
+// TEST INFRASTRUCTURE ONLY -- stand-alone host program around baseflow_host.hpp: the two catchment-baseflow entry points and
+// gw_exp under the call records of tests/_hostprog.hpp (tests/test_baseflow_host.py; tests/baseflow_host writes the records and
+// passes an array of no elements as a null pointer).  Never built or used by the product.
 //
-// Reads calls of the two catchment-baseflow entry points (and of gw_exp) from a binary file, runs each through its host-side
-// launcher and writes the output arrays, so tests/test_baseflow_host.py can hold the SAME source the GPU executes against the
-// numpy statement of the definition -- also in an AddressSanitizer + UBSan build, which needs nothing loaded into python.  Every
-// array is allocated at exactly its stated size (an array of no elements is a null pointer), so a read or write past an end is
-// a finding.  Never built or used by the product.
-//
-// File format (native endianness).  Input: int32 n_calls, then per call eight int32 and one fp64 (dt_h)
-//   forward (0):  0, T, B, has_state_in, wants_s, wants_state_out, 0, 0;  par [3 B], r [T B], state_in [B] if has_state_in
-//   adjoint (1):  1, T, B, has_state_in, has_gs, wants_gpar, wants_gstate, 0;  par [3 B], gq [T B], gs [T B] if has_gs, r [T B],
-//                 s [T B], state_in [B] if has_state_in
-//   gw_exp  (2):  2, n, 0, 0, 0, 0, 0, 0;  z [n]
-// Output: per call q [T B] (+ s [T B]) (+ state_out [B]), or gr [T B] (+ gpar [3 B]) (+ gstate [B]), or gw_exp(z) [n].  An output
-// starts as all-ones bytes (NaN): it is written, not added to.
-#include <cstdio>
-#include <cstring>
-#include <memory>
-
+// Calls (ints; doubles; arrays, all fp64)
+//   0 forward:  T, B; dt_h;  r [T B], par [3 B], state_in [B] or absent, state_out [B], q [T B], s [T B]
+//   1 adjoint:  T, B; dt_h;  gq [T B], gs [T B] or absent, r, s [T B], par [3 B], state_in, gr [T B], gpar [3 B], gstate [B]
+//   2 gw_exp:   n;  z [n], out [n]
 #include "baseflow_host.hpp"
 
-namespace {
+#include "../_hostprog.hpp"
 
-struct Array {
-  std::unique_ptr<double[]> mem;
-  size_t n = 0;
-  double *get() const { return n ? mem.get() : nullptr; }
-  void size(size_t count) {
-    n = count;
-    if (n) mem.reset(new double[n]);
-  }
-  bool read(FILE *in, size_t count) {
-    size(count);
-    return n == 0 || fread(mem.get(), sizeof(double), n, in) == n;
-  }
-  void blank(size_t count) {
-    size(count);
-    if (n) memset(mem.get(), 0xFF, n * sizeof(double));
-  }
-  bool write(FILE *out) const { return n == 0 || fwrite(mem.get(), sizeof(double), n, out) == n; }
-};
-
-int run_call(FILE *in, FILE *out) {
-  int32_t h[8];
-  double dt_h = 0.0;
-  if (fread(h, 4, 8, in) != 8 || fread(&dt_h, 8, 1, in) != 1 || h[1] < 0 || h[2] < 0) return 2;
-  const int32_t op = h[0], T = h[1], B = h[2];
-  const size_t TB = (size_t)T * (size_t)B;
-  Array par, r, s, gq, gs, state_in, o0, o1, o2;
-  if (op == 0) {
-    if (!par.read(in, 3 * (size_t)B) || !r.read(in, TB) || (h[3] && !state_in.read(in, B))) return 2;
-    o0.blank(TB);
-    if (h[4]) o1.blank(TB);
-    if (h[5]) o2.blank(B);
-    if (baseflowhost_catchment_baseflow(r.get(), T, B, par.get(), dt_h, state_in.get(), o2.get(), o0.get(), o1.get()) != 0) return 4;
-  } else if (op == 1) {
-    if (!par.read(in, 3 * (size_t)B) || !gq.read(in, TB) || (h[4] && !gs.read(in, TB)) || !r.read(in, TB) || !s.read(in, TB) ||
-        (h[3] && !state_in.read(in, B)))
-      return 2;
-    o0.blank(TB);
-    if (h[5]) o1.blank(3 * (size_t)B);
-    if (h[6]) o2.blank(B);
-    if (baseflowhost_catchment_baseflow_grad(gq.get(), gs.get(), r.get(), s.get(), T, B, par.get(), dt_h, state_in.get(), o0.get(), o1.get(),
-                                             o2.get()) != 0)
-      return 4;
-  } else if (op == 2) {
-    if (!r.read(in, T)) return 2;
-    o0.blank(T);
-    baseflowhost_gw_exp(r.get(), T, o0.get());
-  } else {
-    return 4;
-  }
-  return o0.write(out) && o1.write(out) && o2.write(out) ? 0 : 3;
-}
-
-}  // namespace
-
-int main(int argc, char **argv) {
-  if (argc != 3) {
-    fprintf(stderr, "usage: %s <input> <output>\n", argv[0]);
-    return 1;
-  }
-  FILE *in = fopen(argv[1], "rb");
-  FILE *out = fopen(argv[2], "wb");
-  if (!in || !out) return 1;
-  int32_t n_calls = 0;
-  if (fread(&n_calls, 4, 1, in) != 1) return 2;
-  for (int k = 0; k < n_calls; k++) {
-    const int rc = run_call(in, out);
-    if (rc) return rc;
-  }
-  fclose(in);
-  return fclose(out) == 0 ? 0 : 3;
+int dispatch(int op, const hostprog::Ints &i, const hostprog::Doubles &d, const hostprog::Arrays &a) {
+  const size_t ni = i.size(), nd = d.size(), na = a.size();
+  auto f = [&a](int k) { return a[k].as<double>(); };
+  if (op == 0 && ni == 2 && nd == 1 && na == 6) return baseflowhost_catchment_baseflow(f(0), i[0], i[1], f(1), d[0], f(2), f(3), f(4), f(5));
+  if (op == 1 && ni == 2 && nd == 1 && na == 9)
+    return baseflowhost_catchment_baseflow_grad(f(0), f(1), f(2), f(3), i[0], i[1], f(4), d[0], f(5), f(6), f(7), f(8));
+  if (op == 2 && ni == 1 && nd == 0 && na == 2) return baseflowhost_gw_exp(f(0), i[0], f(1)), 0;
+  return 4;
 }

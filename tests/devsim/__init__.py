@@ -69,14 +69,11 @@ def prebuild(layers=(2, 3, 4)):
         list(ex.map(lib, layers))
 
 
-class _PostLibrary:
-    """libposthost.so (tests/post_host) under the HIP library's names: lgar_<name>(arguments, stream) is posthost_<name>(arguments).
-    The catchment sums run one row per wave, the kernel the library itself picks for all but huge jobs (the same bits)."""
-
-    def __getattr__(self, name):
-        fn = getattr(post_host.library(), "posthost_" + name[len("lgar_"):])
-        tail = (1,) if name == "lgar_catchment_sums" else ()
-        return lambda *args: fn(*args[:-1], *tail)
+def _PostLibrary():
+    """libposthost.so (tests/post_host) under the HIP library's names.  The catchment sums run one row per wave, the kernel the
+    library itself picks for all but huge jobs (the same bits)."""
+    return _hostbuild.AsHipLibrary(("", "posthost", post_host.library),
+                                   hook=lambda name, fn: (lambda *args: fn(*args[:-1], 1)) if name == "lgar_catchment_sums" else None)
 
 
 class SimCatchmentMap(CatchmentMap):

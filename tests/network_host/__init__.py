@@ -4,36 +4,24 @@ network_host.cpp is the stand-alone program around them (run() below; also built
 libnetworkhost.so the same header as a shared library (library(): what SimCatchmentNetwork puts behind the product's calling
 surface).  The numpy statement of the definition (include/lgar.h, lgar_network_route / lgar_network_route_grad; DESIGN.md section
 14) -- route_ref, adjoint_ref and coef_grad_ref: plain loops over rows and over the reaches in `order`, a level's reaches side by
-side -- the topology builders and the data of the tests' cases live here too.  Never imported by the product package.
+side -- the topology builders and the data of the tests' cases live here too.
+The build, the program's call records (tests/_hostprog.hpp) and same_bits are tests/_hostbuild.py's: UNIT below.
+Never imported by the product package.
 """
 import ctypes as C
 import os
-import struct
-import tempfile
 
 import numpy as np
 
 import _hostbuild
-from _hostbuild import CSRC, ROOT
+from _hostbuild import f64, i32, out, same_bits  # noqa: F401
 from lgar_py_amd.network import CatchmentNetwork
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_HPP = os.path.join(_HERE, "network_host.hpp")
-_DEPS = [os.path.join(CSRC, "lgar_network.hpp"), os.path.join(ROOT, "include", "lgar.h")]
 SHAPE_T = (0, 1, 2, 7, 8, 9, 17)  # around the row chunk of 8
 COEFS = ("muskingum", "accumulate", "lag", "mixed")
 
 
-def same_bits(a, b):
-    """Bit-for-bit equality of two fp64 arrays (NaNs must sit in the same places)."""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.shape != b.shape or a.dtype != np.float64 or b.dtype != np.float64:
-        return False
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool((na == nb).all() and (a.view(np.uint64)[~na] == b.view(np.uint64)[~nb]).all())
-
-
-# ---- topologies ------------------------------------------------------------------------------------------------------------
 class Topology:
     """The arrays of include/lgar.h for a `down` array, built by plain loops (independently of lgar_py_amd.network): level,
     order (by level, then index), level_ptr, up_ptr / up_idx (ascending within a list)."""
@@ -251,25 +239,14 @@ def case_data(rng, T, B, kind):
 
 
 # ---- the host build --------------------------------------------------------------------------------------------------------
-def program(sanitize=False):
-    """The host program, built on first use with the ROCm clang (sanitize: AddressSanitizer + UBSan, any finding aborts)."""
-    return _hostbuild.build(os.path.join(_HERE, "network_host_san" if sanitize else "network_host"), os.path.join(_HERE, "network_host.cpp"),
-                            [_HPP] + _DEPS, _hostbuild.SANITIZE if sanitize else [], "the catchment-network host program")
-
-
-_lib = None
+UNIT = _hostbuild.HostUnit(_HERE, "network_host", "networkhost", ["lgar_network.hpp"], "catchment-network")
 
 
 def library():
     """libnetworkhost.so: networkhost_<entry point>(the arguments of include/lgar.h without the stream), loaded once."""
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(_hostbuild.build(os.path.join(_HERE, "libnetworkhost.so"), _HPP, _DEPS, ["-fPIC", "-shared"],
-                                       "the catchment-network host library"))
-        i32, vp = C.c_int32, C.c_void_p
-        _lib.networkhost_network_route.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp]
-        _lib.networkhost_network_route_grad.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp]
-    return _lib
+    i32, vp = C.c_int32, C.c_void_p
+    return UNIT.library({"network_route": [vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp],
+                         "network_route_grad": [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp]})
 
 
 def run(cases, sanitize=False):
@@ -277,54 +254,25 @@ def run(cases, sanitize=False):
     ("route", topo, x, coef, state_in or None, want_state) gives (y, state_out or None);
     ("grad", topo, gy, coef, x, y, state_in) -- x = y = None: no coefficient gradient -- gives (gx, gc or None).
     topo: anything with the attributes of Topology (the arrays go to the program as they are: a test may corrupt them)."""
-    cases = list(cases)
-    blob, shapes = [struct.pack("i", len(cases))], []
-    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64).tobytes()
-    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).tobytes()
+    calls, results = [], []
     for case in cases:
         op, topo, z, coef = case[:4]
         T, B = np.asarray(z).shape
         assert B == topo.B and np.asarray(coef).shape == (3, B) and op in ("route", "grad")
+        ints = (T, B, len(topo.up_idx), topo.n_levels)
         if op == "route":
-            state, wants = case[4], bool(case[5])
-            blob += [struct.pack("8i", 0, T, B, len(topo.up_idx), topo.n_levels, state is not None, wants, 0), f64(coef), f64(z)]
-            blob += ([f64(state)] if state is not None else []) + [i32(topo.up_ptr), i32(topo.up_idx), i32(topo.order), i32(topo.level_ptr)]
-            shapes.append(((T, B), (2, B) if wants else None))
+            y, state_out = out(True, T, B), out(case[5], 2, B)
+            calls.append((0, ints, (), (f64(z), f64(coef), i32(topo.up_ptr), i32(topo.up_idx), i32(topo.order), i32(topo.level_ptr), f64(case[4]),
+                                        state_out, y)))
+            results.append((y, state_out))
         else:
             x, y, state = case[4], case[5], case[6]
-            wants = x is not None
-            blob += [struct.pack("8i", 1, T, B, len(topo.up_idx), topo.n_levels, state is not None, wants, 0), f64(coef), f64(z),
-                     i32(topo.down), i32(topo.order), i32(topo.level_ptr)]
-            if wants:
-                blob += [f64(x), f64(y)] + ([f64(state)] if state is not None else []) + [i32(topo.up_ptr), i32(topo.up_idx)]
-            shapes.append(((T, B), (3, B) if wants else None))
-    with tempfile.TemporaryDirectory() as tmp:
-        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
-        with open(fin, "wb") as fh:
-            fh.write(b"".join(blob))
-        _hostbuild.run_clean([program(sanitize), fin, fout])
-        raw = open(fout, "rb").read()
-    at, out = 0, []
-    for pair in shapes:
-        got = []
-        for shape in pair:
-            if shape is None:
-                got.append(None)
-                continue
-            n = shape[0] * shape[1] * 8
-            got.append(np.frombuffer(raw[at:at + n], dtype=np.float64).reshape(shape).copy())
-            at += n
-        out.append(tuple(got))
-    assert at == len(raw)
-    return out
-
-
-class _NetworkLibrary:
-    """libnetworkhost.so under the HIP library's names: lgar_<name>(arguments, stream) is networkhost_<name>(arguments)."""
-
-    def __getattr__(self, name):
-        fn = getattr(library(), "networkhost_" + name[len("lgar_"):])
-        return lambda *args: fn(*args[:-1])
+            gx, gc = out(True, T, B), out(x is not None, 3, B)
+            more = (f64(x), f64(y), i32(topo.up_ptr), i32(topo.up_idx), f64(state)) if x is not None else (None,) * 5
+            calls.append((1, ints, (), (f64(z), f64(coef), i32(topo.down), i32(topo.order), i32(topo.level_ptr), gx, *more, gc)))
+            results.append((gx, gc))
+    UNIT.run_calls(calls, sanitize)
+    return [_hostbuild.values(r) for r in results]
 
 
 class SimCatchmentNetwork(CatchmentNetwork):
@@ -334,4 +282,4 @@ class SimCatchmentNetwork(CatchmentNetwork):
         super().__init__(downstream, device="cpu")
 
     def _open(self):
-        return _NetworkLibrary()
+        return _hostbuild.AsHipLibrary(("", "networkhost", library))

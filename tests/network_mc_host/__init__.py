@@ -4,27 +4,25 @@ network_mc_host.cpp is the stand-alone program around them (run() below; also bu
 libnetworkmchost.so the same header as a shared library (library(): what SimCatchmentNetworkMC puts behind the product's calling
 surface).  The numpy statement of the definition (include/lgar.h, lgar_network_route_mc / lgar_network_route_mc_grad; DESIGN.md
 section 17) -- mc_ln_ref, route_mc_ref, route_mc_grad_ref and regimes: plain loops over rows and over the reaches in `order`, a
-level's reaches side by side -- and the data of the tests' cases live here too; the topologies, the inflow fold and same_bits are
-tests/network_host's, gw_exp_ref is tests/baseflow_host's.  Never imported by the product package.
+level's reaches side by side -- and the data of the tests' cases live here too; the topologies and the inflow fold are
+tests/network_host's, gw_exp_ref is tests/baseflow_host's.
+The build, the program's call records (tests/_hostprog.hpp) and same_bits are tests/_hostbuild.py's: UNIT below.
+Never imported by the product package.
 """
 import ctypes as C
 import os
-import struct
-import tempfile
 from fractions import Fraction
 
 import numpy as np
 
 import _hostbuild
 import network_host as NH
-from _hostbuild import CSRC, ROOT
+from _hostbuild import f64, i32, out
 from baseflow_host import LN2_HI, LN2_LO, ZMAX, gw_exp_ref
 from lgar_py_amd.network import CatchmentNetwork
 from network_host import Topology, same_bits  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_HPP = os.path.join(_HERE, "network_mc_host.hpp")
-_DEPS = [os.path.join(CSRC, f) for f in ("lgar_network_mc.hpp", "lgar_network.hpp", "lgar_baseflow.hpp")] + [os.path.join(ROOT, "include", "lgar.h")]
 SHAPE_T = (0, 1, 2, 7, 8, 9, 17)  # around the row chunk of 8
 SQRT_HALF = float.fromhex("0x1.6a09e667f3bcdp-1")
 COEF = [float(Fraction(1, 2 * j + 1)) for j in range(11)]  # Fraction -> float rounds correctly
@@ -201,29 +199,16 @@ def embed(rng, topo, M):
 
 
 # ---- the host build --------------------------------------------------------------------------------------------------------
-def program(sanitize=False):
-    """The host program, built on first use with the ROCm clang (sanitize: AddressSanitizer + UBSan, any finding aborts)."""
-    return _hostbuild.build(os.path.join(_HERE, "network_mc_host_san" if sanitize else "network_mc_host"),
-                            os.path.join(_HERE, "network_mc_host.cpp"), [_HPP] + _DEPS, _hostbuild.SANITIZE if sanitize else [],
-                            "the Muskingum-Cunge network host program")
-
-
-_lib = None
+UNIT = _hostbuild.HostUnit(_HERE, "network_mc_host", "networkmchost", ["lgar_network_mc.hpp", "lgar_network.hpp", "lgar_baseflow.hpp"],
+                           "Muskingum-Cunge network")
 
 
 def library():
     """libnetworkmchost.so: networkmchost_<entry point>(the arguments of include/lgar.h without the stream), loaded once."""
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(_hostbuild.build(os.path.join(_HERE, "libnetworkmchost.so"), _HPP, _DEPS, ["-fPIC", "-shared"],
-                                       "the Muskingum-Cunge network host library"))
-        i32, vp, dbl = C.c_int32, C.c_void_p, C.c_double
-        _lib.networkmchost_network_route_mc.argtypes = [vp, i32, i32, vp, dbl, dbl, dbl, vp, vp, i32, vp, vp, i32, vp, vp, vp]
-        _lib.networkmchost_network_route_mc_grad.argtypes = [vp, i32, i32, vp, dbl, dbl, dbl, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp,
-                                                             vp, vp]
-        _lib.networkmchost_mc_ln.argtypes = [vp, i32, vp]
-        _lib.networkmchost_mc_ln.restype = None
-    return _lib
+    i32, vp, dbl = C.c_int32, C.c_void_p, C.c_double
+    return UNIT.library({"network_route_mc": [vp, i32, i32, vp, dbl, dbl, dbl, vp, vp, i32, vp, vp, i32, vp, vp, vp],
+                         "network_route_mc_grad": [vp, i32, i32, vp, dbl, dbl, dbl, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp],
+                         "mc_ln": [vp, i32, vp]}, {"mc_ln": None})
 
 
 def run(cases, sanitize=False):
@@ -232,63 +217,40 @@ def run(cases, sanitize=False):
     ("grad", topo, gy, x, y, par, dt_h, (rmin, rmax), state_in or None, want_gpar, want_gstate) gives (gx, gpar or None, gstate or None);
     ("ln", x) gives (mc_ln(x),).
     topo: anything with the attributes of Topology (the arrays go to the program as they are: a test may corrupt them)."""
-    cases = list(cases)
-    blob, shapes = [struct.pack("i", len(cases))], []
-    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64).tobytes()
-    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).tobytes()
+    calls, results = [], []
     for case in cases:
         op = case[0]
         if op == "ln":
             v = np.asarray(case[1], dtype=np.float64).ravel()
-            blob += [struct.pack("8i3d", 2, len(v), 0, 0, 0, 0, 0, 0, 1.0, 1.0, 1.0), f64(v)]
-            shapes.append(((len(v),),))
+            results.append((out(True, len(v)),))
+            calls.append((2, (len(v),), (), (v, results[-1][0])))
             continue
         topo = case[1]
         T, B = np.asarray(case[2]).shape
         assert B == topo.B and op in ("route", "grad")
+        ints = (T, B, len(topo.up_idx), topo.n_levels)
         if op == "route":
             x, par, dt_h, (rmin, rmax), state, want = case[2:]
             assert np.asarray(par).shape == (4, B)
-            blob += [struct.pack("8i3d", 0, T, B, len(topo.up_idx), topo.n_levels, state is not None, bool(want), 0, dt_h, rmin, rmax),
-                     f64(par), f64(x)] + ([f64(state)] if state is not None else [])
-            blob += [i32(topo.up_ptr), i32(topo.up_idx), i32(topo.order), i32(topo.level_ptr)]
-            shapes.append(((T, B), (2, B) if want else None))
+            y, state_out = out(True, T, B), out(want, 2, B)
+            calls.append((0, ints, (dt_h, rmin, rmax), (f64(x), f64(par), i32(topo.up_ptr), i32(topo.up_idx), i32(topo.order), i32(topo.level_ptr),
+                                                        f64(state), state_out, y)))
+            results.append((y, state_out))
         else:
             gy, x, y, par, dt_h, (rmin, rmax), state, want_par, want_state = case[2:]
             assert np.asarray(par).shape == (4, B) and np.asarray(x).shape == (T, B) and np.asarray(y).shape == (T, B)
-            blob += [struct.pack("8i3d", 1, T, B, len(topo.up_idx), topo.n_levels, state is not None, int(bool(want_par)) + 2 * int(bool(want_state)),
-                                 0, dt_h, rmin, rmax), f64(par), f64(gy), f64(x), f64(y)] + ([f64(state)] if state is not None else [])
-            blob += [i32(topo.down), i32(topo.order), i32(topo.level_ptr), i32(topo.up_ptr), i32(topo.up_idx)]
-            shapes.append(((T, B), (3, B) if want_par else None, (2, B) if want_state else None))
-    with tempfile.TemporaryDirectory() as tmp:
-        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
-        with open(fin, "wb") as fh:
-            fh.write(b"".join(blob))
-        _hostbuild.run_clean([program(sanitize), fin, fout])
-        raw = open(fout, "rb").read()
-    at, out = 0, []
-    for group in shapes:
-        got = []
-        for shape in group:
-            if shape is None:
-                got.append(None)
-                continue
-            n = int(np.prod(shape)) * 8
-            got.append(np.frombuffer(raw[at:at + n], dtype=np.float64).reshape(shape).copy())
-            at += n
-        out.append(tuple(got))
-    assert at == len(raw)
-    return out
+            gx, gpar, gstate = out(True, T, B), out(want_par, 3, B), out(want_state, 2, B)
+            calls.append((1, ints, (dt_h, rmin, rmax), (f64(gy), f64(par), i32(topo.down), i32(topo.order), i32(topo.level_ptr), gx, f64(x), f64(y),
+                                                        i32(topo.up_ptr), i32(topo.up_idx), f64(state), gpar, gstate)))
+            results.append((gx, gpar, gstate))
+    UNIT.run_calls(calls, sanitize)
+    return [_hostbuild.values(r) for r in results]
 
 
-class _NetworkLibrary:
-    """libnetworkmchost.so and tests/network_host's libnetworkhost.so under the HIP library's names: lgar_<name>(arguments,
-    stream) is networkmchost_<name>(arguments), or networkhost_<name>(arguments) for the linear route."""
-
-    def __getattr__(self, name):
-        short = name[len("lgar_"):]
-        fn = getattr(library(), "networkmchost_" + short) if short.startswith("network_route_mc") else getattr(NH.library(), "networkhost_" + short)
-        return lambda *args: fn(*args[:-1])
+def hip_library(*first):
+    """The network host libraries under the HIP library's names (_hostbuild.AsHipLibrary): `first`, then this unit's for
+    network_route_mc*, then tests/network_host's for the linear route."""
+    return _hostbuild.AsHipLibrary(*first, ("network_route_mc", "networkmchost", library), ("", "networkhost", NH.library))
 
 
 class SimCatchmentNetworkMC(CatchmentNetwork):
@@ -299,4 +261,4 @@ class SimCatchmentNetworkMC(CatchmentNetwork):
         super().__init__(downstream, device="cpu")
 
     def _open(self):
-        return _NetworkLibrary()
+        return hip_library()

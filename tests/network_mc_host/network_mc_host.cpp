@@ -1,107 +1,27 @@
-// TEST INFRASTRUCTURE ONLY -- stand-alone host program around network_mc_host.hpp.
+// TEST INFRASTRUCTURE ONLY -- stand-alone host program around network_mc_host.hpp: the two Muskingum-Cunge network entry points
+// and mc_ln under the call records of tests/_hostprog.hpp (tests/test_network_mc_host.py; tests/network_mc_host writes the records
+// and passes an array of no elements as a null pointer).  The topology is taken as the file gives it, so a read or write past an
+// end under a corrupt topology is a finding.  Never built or used by the product.
 //
-// Reads calls of the two Muskingum-Cunge network entry points (and of mc_ln) from a binary file, runs each through its host-side
-// launcher and writes the output arrays, so tests/test_network_mc_host.py can hold the SAME source the GPU executes against the
-// numpy statement of the definition -- also in an AddressSanitizer + UBSan build, which needs nothing loaded into python.  Every
-// array is allocated at exactly its stated size (an array of no elements is a null pointer), and the topology is taken as the
-// file gives it, so a read or write past an end under a corrupt topology is a finding.  Never built or used by the product.
-//
-// File format (native endianness).  Input: int32 n_calls, then per call eight int32
-//   operation (0 forward, 1 adjoint, 2 mc_ln), T, B, E, n_levels, has_state_in, wants (forward: 1 = state_out; adjoint: 1 = gpar,
-//   2 = gstate), 0
-// then fp64 dt_h, rmin, rmax and
-//   forward:  par [4 B], x [T B], state_in [2 B] if has_state_in, up_ptr [B + 1], up_idx [E], order [B], level_ptr [n_levels + 1]
-//   adjoint:  par [4 B], gy [T B], x [T B], y [T B], state_in [2 B] if has_state_in, down [B], order [B], level_ptr [n_levels + 1],
-//             up_ptr [B + 1], up_idx [E]
-//   mc_ln:    x [T]
-// Output: per call y [T B] (+ state_out [2 B]), or gx [T B] (+ gpar [3 B]) (+ gstate [2 B]), or mc_ln(x) [T].  An output starts as
-// all-ones bytes (NaN): it is written, not added to.
-#include <cstdio>
-#include <cstring>
-#include <memory>
-
+// Calls (ints; doubles; arrays: fp64, the topology int32)
+//   0 forward:  T, B, E, n_levels; dt_h, rmin, rmax;  x [T B], par [4 B], up_ptr [B + 1], up_idx [E], order [B],
+//               level_ptr [n_levels + 1], state_in [2 B] or absent, state_out [2 B], y [T B]
+//   1 adjoint:  T, B, E, n_levels; dt_h, rmin, rmax;  gy [T B], par, down [B], order, level_ptr, gx [T B], x, y [T B], up_ptr,
+//               up_idx, state_in, gpar [3 B], gstate [2 B]
+//   2 mc_ln:    n;  x [n], out [n]
 #include "network_mc_host.hpp"
 
-namespace {
+#include "../_hostprog.hpp"
 
-template <typename V> struct Array {
-  std::unique_ptr<V[]> mem;
-  size_t n = 0;
-  V *get() const { return n ? mem.get() : nullptr; }
-  void size(size_t count) {
-    n = count;
-    if (n) mem.reset(new V[n]);
-  }
-  bool read(FILE *in, size_t count) {
-    size(count);
-    return n == 0 || fread(mem.get(), sizeof(V), n, in) == n;
-  }
-  void blank(size_t count) {
-    size(count);
-    if (n) memset(mem.get(), 0xFF, n * sizeof(V));
-  }
-  bool write(FILE *out) const { return n == 0 || fwrite(mem.get(), sizeof(V), n, out) == n; }
-};
-
-int run_call(FILE *in, FILE *out) {
-  int32_t h[8];
-  double sc[3];
-  if (fread(h, 4, 8, in) != 8 || h[1] < 0 || h[2] < 0 || h[3] < 0 || h[4] < 0 || fread(sc, 8, 3, in) != 3) return 2;
-  const int32_t op = h[0], T = h[1], B = h[2], E = h[3], L = h[4];
-  const bool has_state = h[5] != 0;
-  const int32_t wants = h[6];
-  const size_t TB = (size_t)T * (size_t)B;
-  Array<double> par, x, y, gy, state_in, result, extra, extra2;
-  Array<int32_t> up_ptr, up_idx, order, level_ptr, down;
-  if (op == 2) {
-    if (!x.read(in, T)) return 2;
-    result.blank(T);
-    networkmchost_mc_ln(x.get(), T, result.get());
-    return result.write(out) ? 0 : 3;
-  }
-  if (!par.read(in, 4 * (size_t)B)) return 2;
-  if (op == 0) {
-    if (!x.read(in, TB) || (has_state && !state_in.read(in, 2 * (size_t)B)) || !up_ptr.read(in, (size_t)B + 1) || !up_idx.read(in, E) ||
-        !order.read(in, B) || !level_ptr.read(in, (size_t)L + 1))
-      return 2;
-    result.blank(TB);
-    if (wants & 1) extra.blank(2 * (size_t)B);
-    if (networkmchost_network_route_mc(x.get(), T, B, par.get(), sc[0], sc[1], sc[2], up_ptr.get(), up_idx.get(), E, order.get(),
-                                       level_ptr.get(), L, state_in.get(), extra.get(), result.get()) != 0)
-      return 4;
-  } else if (op == 1) {
-    if (!gy.read(in, TB) || !x.read(in, TB) || !y.read(in, TB) || (has_state && !state_in.read(in, 2 * (size_t)B)) || !down.read(in, B) ||
-        !order.read(in, B) || !level_ptr.read(in, (size_t)L + 1) || !up_ptr.read(in, (size_t)B + 1) || !up_idx.read(in, E))
-      return 2;
-    result.blank(TB);
-    if (wants & 1) extra.blank(3 * (size_t)B);
-    if (wants & 2) extra2.blank(2 * (size_t)B);
-    if (networkmchost_network_route_mc_grad(gy.get(), T, B, par.get(), sc[0], sc[1], sc[2], down.get(), order.get(), level_ptr.get(), L,
-                                            result.get(), x.get(), y.get(), up_ptr.get(), up_idx.get(), E, state_in.get(), extra.get(),
-                                            extra2.get()) != 0)
-      return 4;
-  } else {
-    return 4;
-  }
-  return result.write(out) && extra.write(out) && extra2.write(out) ? 0 : 3;
-}
-
-}  // namespace
-
-int main(int argc, char **argv) {
-  if (argc != 3) {
-    fprintf(stderr, "usage: %s <input> <output>\n", argv[0]);
-    return 1;
-  }
-  FILE *in = fopen(argv[1], "rb");
-  FILE *out = fopen(argv[2], "wb");
-  if (!in || !out) return 1;
-  int32_t n_calls = 0;
-  if (fread(&n_calls, 4, 1, in) != 1) return 2;
-  for (int k = 0; k < n_calls; k++) {
-    const int rc = run_call(in, out);
-    if (rc) return rc;
-  }
-  fclose(in);
-  return fclose(out) == 0 ? 0 : 3;
+int dispatch(int op, const hostprog::Ints &i, const hostprog::Doubles &d, const hostprog::Arrays &a) {
+  const size_t ni = i.size(), nd = d.size(), na = a.size();
+  auto f = [&a](int k) { return a[k].as<double>(); };
+  auto n = [&a](int k) { return a[k].as<int32_t>(); };
+  if (op == 0 && ni == 4 && nd == 3 && na == 9)
+    return networkmchost_network_route_mc(f(0), i[0], i[1], f(1), d[0], d[1], d[2], n(2), n(3), i[2], n(4), n(5), i[3], f(6), f(7), f(8));
+  if (op == 1 && ni == 4 && nd == 3 && na == 13)
+    return networkmchost_network_route_mc_grad(f(0), i[0], i[1], f(1), d[0], d[1], d[2], n(2), n(3), n(4), i[3], f(5), f(6), f(7), n(8), n(9),
+                                               i[2], f(10), f(11), f(12));
+  if (op == 2 && ni == 1 && nd == 0 && na == 2) return networkmchost_mc_ln(f(0), i[0], f(1)), 0;
+  return 4;
 }

@@ -5,29 +5,26 @@ libnetworkpoolhost.so the same header as a shared library (library(): what SimCa
 calling surface).  The numpy statement of the definition (include/lgar.h, lgar_network_route_pool / lgar_network_route_pool_grad;
 DESIGN.md section 18) -- route_pool_ref, route_pool_grad_ref and pool_regimes: plain loops over rows and over the nodes in the
 pool-aware `order`, a level's reaches side by side and then its pools side by side -- and the data of the tests' cases live here
-too; the topologies, the inflow fold and same_bits are tests/network_host's, the reach row (_row), mc_ln_ref and the reach data are
-tests/network_mc_host's, gw_exp_ref is tests/baseflow_host's.  Never imported by the product package.
+too; the topologies and the inflow fold are tests/network_host's, the reach row (_row), mc_ln_ref and the reach data are
+tests/network_mc_host's, gw_exp_ref is tests/baseflow_host's.
+The build, the program's call records (tests/_hostprog.hpp) and same_bits are tests/_hostbuild.py's: UNIT below.
+Never imported by the product package.
 """
 import ctypes as C
 import os
-import struct
-import tempfile
 
 import numpy as np
 
 import _hostbuild
 import network_host as NH
 import network_mc_host as MH
-from _hostbuild import CSRC, ROOT
+from _hostbuild import f64, i32, out
 from baseflow_host import ZMAX, gw_exp_ref
 from lgar_py_amd.network import CatchmentNetwork
 from network_host import Topology, same_bits  # noqa: F401
 from network_mc_host import mc_ln_ref
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_HPP = os.path.join(_HERE, "network_pool_host.hpp")
-_DEPS = [os.path.join(CSRC, f) for f in ("lgar_network_pool.hpp", "lgar_network_mc.hpp", "lgar_network.hpp", "lgar_baseflow.hpp")] + \
-        [os.path.join(ROOT, "include", "lgar.h")]
 SHAPE_T = (0, 1, 2, 7, 8, 9, 17)  # around the row chunk of 8
 PNARROW, PWIDE = (2.0 ** -20, 2.0 ** 20), (2.0 ** -60, 2.0 ** 60)  # prmin, prmax: the Python layer's default, and the widest allowed
 PLACEMENTS = ("none", "all", "outlets", "headwaters", "alternate", "random10", "level64", "level65", "poollevel")
@@ -332,30 +329,17 @@ def case_data(rng, pt, T, wide=False):
 
 
 # ---- the host build --------------------------------------------------------------------------------------------------------
-def program(sanitize=False):
-    """The host program, built on first use with the ROCm clang (sanitize: AddressSanitizer + UBSan, any finding aborts)."""
-    return _hostbuild.build(os.path.join(_HERE, "network_pool_host_san" if sanitize else "network_pool_host"),
-                            os.path.join(_HERE, "network_pool_host.cpp"), [_HPP] + _DEPS, _hostbuild.SANITIZE if sanitize else [],
-                            "the reach-and-pool network host program")
-
-
-_lib = None
+UNIT = _hostbuild.HostUnit(_HERE, "network_pool_host", "networkpoolhost",
+                           ["lgar_network_pool.hpp", "lgar_network_mc.hpp", "lgar_network.hpp", "lgar_baseflow.hpp"], "reach-and-pool network")
 
 
 def library():
     """libnetworkpoolhost.so: networkpoolhost_<entry point>(the arguments of include/lgar.h without the stream), loaded once."""
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(_hostbuild.build(os.path.join(_HERE, "libnetworkpoolhost.so"), _HPP, _DEPS, ["-fPIC", "-shared"],
-                                       "the reach-and-pool network host library"))
-        i32, vp, dbl = C.c_int32, C.c_void_p, C.c_double
-        _lib.networkpoolhost_network_route_pool.argtypes = [vp, i32, i32, vp, vp, i32, dbl, dbl, dbl, dbl, dbl, vp, vp, i32, vp, vp, vp, i32, vp, vp,
-                                                            vp, vp, vp]
-        _lib.networkpoolhost_network_route_pool_grad.argtypes = [vp, i32, i32, vp, vp, i32, dbl, dbl, dbl, dbl, dbl, vp, vp, vp, vp, i32, vp, vp, vp,
-                                                                 vp, vp, vp, vp, i32, vp, vp, vp, vp]
-        _lib.networkpoolhost_release.argtypes = [vp, vp, i32, dbl, dbl, vp]
-        _lib.networkpoolhost_release.restype = None
-    return _lib
+    i32, vp, dbl = C.c_int32, C.c_void_p, C.c_double
+    return UNIT.library({"network_route_pool": [vp, i32, i32, vp, vp, i32, dbl, dbl, dbl, dbl, dbl, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp],
+                         "network_route_pool_grad": [vp, i32, i32, vp, vp, i32, dbl, dbl, dbl, dbl, dbl, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp,
+                                                     vp, i32, vp, vp, vp, vp],
+                         "release": [vp, vp, i32, dbl, dbl, vp]}, {"release": None})
 
 
 def run(cases, sanitize=False):
@@ -366,75 +350,38 @@ def run(cases, sanitize=False):
         (gx, gpar_mc or None, gpool or None, gstate or None);
     ("release", rc, m, prr) gives (the row's Ql for cq = 1,).
     pt: anything with the attributes of PoolTopology (the arrays go to the program as they are: a test may corrupt them)."""
-    cases = list(cases)
-    blob, shapes = [struct.pack("i", len(cases))], []
-    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64).tobytes()
-    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).tobytes()
+    calls, results = [], []
     for case in cases:
         op = case[0]
         if op == "release":
             v, m, prr = (np.asarray(case[1], dtype=np.float64).ravel(), np.asarray(case[2], dtype=np.float64).ravel(), case[3])
             assert len(v) == len(m)
-            blob += [struct.pack("10i5d", 2, len(v), 0, 0, 0, 0, 0, 0, 0, 0, 1.0, 1.0, 1.0, prr[0], prr[1]), f64(v), f64(m)]
-            shapes.append(((len(v),),))
+            results.append((out(True, len(v)),))
+            calls.append((2, (len(v),), tuple(prr), (v, m, results[-1][0])))
             continue
         pt = case[1]
         T, B = np.asarray(case[2]).shape
         P = pt.P
         assert B == pt.B and op in ("route", "grad")
-        slot = [i32(pt.pool_slot)] if P else []
+        ints, slot = (T, B, len(pt.up_idx), pt.n_levels, P), i32(pt.pool_slot) if P else None
         if op == "route":
             x, par_mc, par_pool, dt_h, rr, prr, state, want_state, want_storage = case[2:]
             assert np.asarray(par_mc).shape == (4, B) and np.asarray(par_pool).shape == (5, P)
-            blob += [struct.pack("10i5d", 0, T, B, len(pt.up_idx), pt.n_levels, P, state is not None,
-                                 int(bool(want_state)) + 2 * int(bool(want_storage)), 0, 0, dt_h, rr[0], rr[1], prr[0], prr[1]),
-                     f64(par_mc), f64(par_pool), f64(x)] + ([f64(state)] if state is not None else [])
-            blob += [i32(pt.up_ptr), i32(pt.up_idx), i32(pt.order), i32(pt.level_ptr), i32(pt.pool_ptr)] + slot
-            shapes.append(((T, B), (2, B) if want_state else None, (T, P) if want_storage else None))
+            y, state_out, storage = out(True, T, B), out(want_state, 2, B), out(want_storage, T, P)
+            calls.append((0, ints, (dt_h, *rr, *prr), (f64(x), f64(par_mc), f64(par_pool), i32(pt.up_ptr), i32(pt.up_idx), i32(pt.order),
+                                                       i32(pt.level_ptr), i32(pt.pool_ptr), slot, f64(state), state_out, y, storage)))
+            results.append((y, state_out, storage))
         else:
             gy, x, y, storage, par_mc, par_pool, dt_h, rr, prr, state, want_par, want_pool, want_state = case[2:]
             assert np.asarray(par_mc).shape == (4, B) and np.asarray(par_pool).shape == (5, P) and np.asarray(x).shape == (T, B)
             assert np.asarray(y).shape == (T, B) and np.asarray(storage).shape == (T, P)
-            blob += [struct.pack("10i5d", 1, T, B, len(pt.up_idx), pt.n_levels, P, state is not None,
-                                 int(bool(want_par)) + 2 * int(bool(want_pool)) + 4 * int(bool(want_state)), 0, 0, dt_h, rr[0], rr[1], prr[0],
-                                 prr[1]), f64(par_mc), f64(par_pool), f64(gy), f64(x), f64(y), f64(storage)]
-            blob += ([f64(state)] if state is not None else []) + [i32(pt.down), i32(pt.order), i32(pt.level_ptr), i32(pt.pool_ptr)] + slot
-            blob += [i32(pt.up_ptr), i32(pt.up_idx)]
-            shapes.append(((T, B), (3, B) if want_par else None, (4, P) if want_pool else None, (2, B) if want_state else None))
-    with tempfile.TemporaryDirectory() as tmp:
-        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
-        with open(fin, "wb") as fh:
-            fh.write(b"".join(blob))
-        _hostbuild.run_clean([program(sanitize), fin, fout])
-        raw = open(fout, "rb").read()
-    at, out = 0, []
-    for group in shapes:
-        got = []
-        for shape in group:
-            if shape is None:
-                got.append(None)
-                continue
-            n = int(np.prod(shape)) * 8
-            got.append(np.frombuffer(raw[at:at + n], dtype=np.float64).reshape(shape).copy())
-            at += n
-        out.append(tuple(got))
-    assert at == len(raw)
-    return out
-
-
-class _NetworkLibrary:
-    """The three network host libraries under the HIP library's names: lgar_<name>(arguments, stream) is
-    networkpoolhost_<name>(arguments), networkmchost_<name>(arguments) or networkhost_<name>(arguments)."""
-
-    def __getattr__(self, name):
-        short = name[len("lgar_"):]
-        if short.startswith("network_route_pool"):
-            fn = getattr(library(), "networkpoolhost_" + short)
-        elif short.startswith("network_route_mc"):
-            fn = getattr(MH.library(), "networkmchost_" + short)
-        else:
-            fn = getattr(NH.library(), "networkhost_" + short)
-        return lambda *args: fn(*args[:-1])
+            gx, gpar, gpool, gstate = out(True, T, B), out(want_par, 3, B), out(want_pool, 4, P), out(want_state, 2, B)
+            calls.append((1, ints, (dt_h, *rr, *prr), (f64(gy), f64(par_mc), f64(par_pool), i32(pt.down), i32(pt.order), i32(pt.level_ptr),
+                                                       i32(pt.pool_ptr), slot, gx, f64(x), f64(y), f64(storage), i32(pt.up_ptr), i32(pt.up_idx),
+                                                       f64(state), gpar, gpool, gstate)))
+            results.append((gx, gpar, gpool, gstate))
+    UNIT.run_calls(calls, sanitize)
+    return [_hostbuild.values(r) for r in results]
 
 
 class SimCatchmentNetworkPool(CatchmentNetwork):
@@ -445,4 +392,4 @@ class SimCatchmentNetworkPool(CatchmentNetwork):
         super().__init__(downstream, device="cpu")
 
     def _open(self):
-        return _NetworkLibrary()
+        return MH.hip_library(("network_route_pool", "networkpoolhost", library))

@@ -3,37 +3,25 @@ host with -DLGAR_DEVSIM) and its front-end.  score_host.hpp holds the host-side 
 score_host.cpp is the stand-alone program around them (run() below; also built with AddressSanitizer + UBSan), libscorehost.so
 the same header as a shared library (library(): what SimCatchmentScore puts behind the product's calling surface).  The numpy
 statement of the definition (include/lgar.h, lgar_catchment_moments / lgar_catchment_moments_grad) --
-moments_ref and grad_ref, plain loops over blocks and rows -- and the data of the tests' cases live here too.  Never imported
-by the product package.
+moments_ref and grad_ref, plain loops over blocks and rows -- and the data of the tests' cases live here too.
+The build, the program's call records (tests/_hostprog.hpp) and same_bits are tests/_hostbuild.py's: UNIT below.
+Never imported by the product package.
 """
 import ctypes as C
 import os
-import struct
-import tempfile
 
 import numpy as np
 
 import _hostbuild
-from _hostbuild import CSRC, ROOT
+from _hostbuild import Out, same_bits  # noqa: F401
 from lgar_py_amd.scores import CatchmentScore
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_HPP = os.path.join(_HERE, "score_host.hpp")
-_DEPS = [os.path.join(CSRC, "lgar_score.hpp"), os.path.join(ROOT, "include", "lgar.h")]
 BLOCK, NMOM = 64, 7  # LGAR_SCORE_BLOCK, LGAR_SCORE_NMOM
 SHAPE_B = (1, 63, 64, 65, 257)
 SHAPE_TO = (0, 1, 63, 64, 65, 129)
 SHAPE_WINDOW = (1, 3, 12)
 GAPS = ("none", "random", "missing", "one_valid", "block", "inf")
-
-
-def same_bits(a, b):
-    """Bit-for-bit equality of two fp64 arrays (NaNs must sit in the same places)."""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.shape != b.shape or a.dtype != np.float64 or b.dtype != np.float64:
-        return False
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool((na == nb).all() and (a.view(np.uint64)[~na] == b.view(np.uint64)[~nb]).all())
 
 
 # ---- the definition, in numpy ----------------------------------------------------------------------------------------------
@@ -178,67 +166,35 @@ def mixed_data(rng, To, B, window, gaps):
 
 
 # ---- the host build --------------------------------------------------------------------------------------------------------
-def program(sanitize=False):
-    """The host program, built on first use with the ROCm clang (sanitize: AddressSanitizer + UBSan, any finding aborts)."""
-    return _hostbuild.build(os.path.join(_HERE, "score_host_san" if sanitize else "score_host"), os.path.join(_HERE, "score_host.cpp"),
-                            [_HPP] + _DEPS, _hostbuild.SANITIZE if sanitize else [], "the catchment-score host program")
+UNIT = _hostbuild.HostUnit(_HERE, "score_host", "scorehost", ["lgar_score.hpp"], "catchment-score")
 
 
 def library():
     """libscorehost.so: scorehost_<entry point>(the arguments of include/lgar.h without the stream), loaded once."""
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(_hostbuild.build(os.path.join(_HERE, "libscorehost.so"), _HPP, _DEPS, ["-fPIC", "-shared"],
-                                       "the catchment-score host library"))
-        i32, vp = C.c_int32, C.c_void_p
-        _lib.scorehost_catchment_moments_workspace.restype = C.c_int64
-        _lib.scorehost_catchment_moments_workspace.argtypes = [i32, i32]
-        _lib.scorehost_catchment_moments.argtypes = [vp, vp, i32, i32, i32, vp, vp]
-        _lib.scorehost_catchment_moments_grad.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
-    return _lib
-
-
-_lib = None
+    i32, vp = C.c_int32, C.c_void_p
+    return UNIT.library({"catchment_moments_workspace": [i32, i32], "catchment_moments": [vp, vp, i32, i32, i32, vp, vp],
+                         "catchment_moments_grad": [vp, vp, i32, i32, i32, vp, vp, vp]}, {"catchment_moments_workspace": C.c_int64})
 
 
 def run(cases, sanitize=False):
     """ONE run of the host program over every case: ("moments", sim, obs, window) gives moments [7, B];
     ("grad", sim, obs, window, moments, coef) gives grad_sim [To * window, B]."""
-    cases = list(cases)
-    blob, shapes = [struct.pack("i", len(cases))], []
     f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    calls, results = [], []
     for op, sim, obs, window, *rest in cases:
         sim, obs = f64(sim), f64(obs)
         To, B = obs.shape
         assert sim.shape == (To * window, B) and op in ("moments", "grad")
-        blob += [struct.pack("4i", op == "grad", To, B, window), sim.tobytes(), obs.tobytes()]
         if op == "grad":
             moments, coef = f64(rest[0]), f64(rest[1])
             assert moments.shape == (NMOM, B) and coef.shape == (4, B)
-            blob += [moments.tobytes(), coef.tobytes()]
-        shapes.append((To * window, B) if op == "grad" else (NMOM, B))
-    with tempfile.TemporaryDirectory() as tmp:
-        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
-        with open(fin, "wb") as fh:
-            fh.write(b"".join(blob))
-        _hostbuild.run_clean([program(sanitize), fin, fout])
-        raw = open(fout, "rb").read()
-    at, out = 0, []
-    for shape in shapes:
-        n = shape[0] * shape[1] * 8
-        out.append(np.frombuffer(raw[at:at + n], dtype=np.float64).reshape(shape).copy())
-        at += n
-    assert at == len(raw)
-    return out
-
-
-class _ScoreLibrary:
-    """libscorehost.so under the HIP library's names: lgar_<name>(arguments, stream) is scorehost_<name>(arguments); the
-    workspace function has no stream."""
-
-    def __getattr__(self, name):
-        fn = getattr(library(), "scorehost_" + name[len("lgar_"):])
-        return fn if name.endswith("_workspace") else (lambda *args: fn(*args[:-1]))
+            results.append(Out(np.float64, To * window, B))
+            calls.append((1, (To, B, window), (), (sim, obs, moments, coef, results[-1])))
+        else:
+            results.append(Out(np.float64, NMOM, B))
+            calls.append((0, (To, B, window), (), (sim, obs, results[-1])))
+    UNIT.run_calls(calls, sanitize)
+    return [r.value for r in results]
 
 
 class SimCatchmentScore(CatchmentScore):
@@ -248,4 +204,5 @@ class SimCatchmentScore(CatchmentScore):
         super().__init__(observations, window=window, warmup=warmup, device="cpu")
 
     def _open(self):
-        return _ScoreLibrary()
+        # (the workspace function has no stream)
+        return _hostbuild.AsHipLibrary(("", "scorehost", library), hook=lambda name, fn: fn if name.endswith("_workspace") else None)

@@ -3,38 +3,26 @@ with -DLGAR_DEVSIM) and its front-end.  snow_host.hpp holds the host-side launch
 stand-alone program around them (run() below; also built with AddressSanitizer + UBSan), libsnowhost.so the same header as a
 shared library (library(): what SimCatchmentSnow puts behind the product's calling surface).  The numpy statement of the
 definition (include/lgar.h, lgar_catchment_snow / lgar_catchment_snow_grad) -- snow_ref, snow_grad_ref and
-regimes: plain loops over rows, the cells side by side -- and the data of the tests' cases live here too.  Never imported by the
-product package.
+regimes: plain loops over rows, the cells side by side -- and the data of the tests' cases live here too.
+The build, the program's call records (tests/_hostprog.hpp) and same_bits are tests/_hostbuild.py's: UNIT below.
+Never imported by the product package.
 """
 import ctypes as C
 import os
-import struct
-import tempfile
 
 import numpy as np
 
 import _hostbuild
-from _hostbuild import CSRC, ROOT
+from _hostbuild import f64, out, same_bits  # noqa: F401
 from lgar_py_amd.snow import CatchmentSnow
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_HPP = os.path.join(_HERE, "snow_host.hpp")
-_DEPS = [os.path.join(CSRC, "lgar_snow.hpp"), os.path.join(ROOT, "include", "lgar.h")]
 SHAPE_B = (1, 2, 63, 64, 65, 257)
 SHAPE_T = (0, 1, 2, 7, 8, 9, 17)  # around the row chunk of 8
 TLO, THI, TM, SFCF, CFMAX, CFR, CWH = range(7)  # the rows of par
 REGIMES = ("lo", "mid", "hi", "melt_limited", "melt_free", "refreeze_limited", "refreeze_free", "over", "hold", "step")
 TIES = ("Ta==tlo", "Ta==thi", "d==0", "pm==ice1", "pr==liq", "liq1==cap")
 TIE_CELLS = {name: 16 + k for k, name in enumerate(TIES)}  # the cells case_data plants the ties in (row 0, with the state given)
-
-
-def same_bits(a, b):
-    """Bit-for-bit equality of two fp64 arrays (NaNs must sit in the same places)."""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.shape != b.shape or a.dtype != np.float64 or b.dtype != np.float64:
-        return False
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool((na == nb).all() and (a.view(np.uint64)[~na] == b.view(np.uint64)[~nb]).all())
 
 
 # ---- the definition, in numpy ----------------------------------------------------------------------------------------------
@@ -220,25 +208,14 @@ def case_data(rng, T, B):
 
 
 # ---- the host build --------------------------------------------------------------------------------------------------------
-def program(sanitize=False):
-    """The host program, built on first use with the ROCm clang (sanitize: AddressSanitizer + UBSan, any finding aborts)."""
-    return _hostbuild.build(os.path.join(_HERE, "snow_host_san" if sanitize else "snow_host"), os.path.join(_HERE, "snow_host.cpp"),
-                            [_HPP] + _DEPS, _hostbuild.SANITIZE if sanitize else [], "the catchment-snowpack host program")
-
-
-_lib = None
+UNIT = _hostbuild.HostUnit(_HERE, "snow_host", "snowhost", ["lgar_snow.hpp"], "catchment-snowpack")
 
 
 def library():
     """libsnowhost.so: snowhost_<entry point>(the arguments of include/lgar.h without the stream), loaded once."""
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(_hostbuild.build(os.path.join(_HERE, "libsnowhost.so"), _HPP, _DEPS, ["-fPIC", "-shared"],
-                                       "the catchment-snowpack host library"))
-        i32, vp, dbl = C.c_int32, C.c_void_p, C.c_double
-        _lib.snowhost_catchment_snow.argtypes = [vp, vp, i32, i32, vp, dbl, vp, vp, vp, vp, vp]
-        _lib.snowhost_catchment_snow_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, dbl, vp, vp, vp, vp, vp]
-    return _lib
+    i32, vp, dbl = C.c_int32, C.c_void_p, C.c_double
+    return UNIT.library({"catchment_snow": [vp, vp, i32, i32, vp, dbl, vp, vp, vp, vp, vp],
+                         "catchment_snow_grad": [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, dbl, vp, vp, vp, vp, vp]})
 
 
 def run(cases, sanitize=False):
@@ -246,55 +223,28 @@ def run(cases, sanitize=False):
     ("fwd", p, ta, par, dt_h, state_in or None, want_pack, want_state) gives (w, ice or None, liq or None, state_out or None);
     ("grad", gw, gice or None, gliq or None, p, ta, ice, liq, par, dt_h, state_in or None, want_gta, want_gpar, want_gstate) gives
     (gp, gta or None, gpar or None, gstate or None).  gice and gliq come together."""
-    cases = list(cases)
-    blob, shapes = [struct.pack("i", len(cases))], []
-    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64).tobytes()
+    calls, results = [], []
     for case in cases:
         if case[0] == "fwd":
             p, ta, par, dt_h, state, want_pack, want_state = case[1:]
             T, B = np.asarray(p).shape
             assert np.asarray(par).shape == (7, B) and np.asarray(ta).shape == (T, B)
-            blob += [struct.pack("8id", 0, T, B, state is not None, bool(want_pack), bool(want_state), 0, 0, dt_h), f64(par), f64(p), f64(ta)]
-            blob += [f64(state)] if state is not None else []
-            shapes.append(((T, B), (T, B) if want_pack else None, (T, B) if want_pack else None, (2, B) if want_state else None))
+            # (an array of no elements is a null pointer: with T = 0 or B = 0 a wanted pack is "neither", which the entry point takes)
+            w, ice, liq, state_out = out(True, T, B), out(want_pack, T, B), out(want_pack, T, B), out(want_state, 2, B)
+            calls.append((0, (T, B), (dt_h,), (f64(p), f64(ta), f64(par), f64(state), state_out, w, ice, liq)))
+            results.append((w, ice, liq, state_out))
         else:
             assert case[0] == "grad"
             gw, gice, gliq, p, ta, ice, liq, par, dt_h, state, want_ta, want_par, want_state = case[1:]
             T, B = np.asarray(p).shape
             assert (gice is None) == (gliq is None) and np.asarray(par).shape == (7, B)
             assert all(np.asarray(a).shape == (T, B) for a in (gw, ta, ice, liq))
-            blob += [struct.pack("8id", 1, T, B, state is not None, gice is not None, bool(want_ta), bool(want_par), bool(want_state), dt_h),
-                     f64(par), f64(gw)]
-            blob += ([f64(gice), f64(gliq)] if gice is not None else []) + [f64(p), f64(ta), f64(ice), f64(liq)]
-            blob += [f64(state)] if state is not None else []
-            shapes.append(((T, B), (T, B) if want_ta else None, (7, B) if want_par else None, (2, B) if want_state else None))
-    with tempfile.TemporaryDirectory() as tmp:
-        fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
-        with open(fin, "wb") as fh:
-            fh.write(b"".join(blob))
-        _hostbuild.run_clean([program(sanitize), fin, fout])
-        raw = open(fout, "rb").read()
-    at, out = 0, []
-    for group in shapes:
-        got = []
-        for shape in group:
-            if shape is None:
-                got.append(None)
-                continue
-            n = int(np.prod(shape)) * 8
-            got.append(np.frombuffer(raw[at:at + n], dtype=np.float64).reshape(shape).copy())
-            at += n
-        out.append(tuple(got))
-    assert at == len(raw)
-    return out
-
-
-class _SnowLibrary:
-    """libsnowhost.so under the HIP library's names: lgar_<name>(arguments, stream) is snowhost_<name>(arguments)."""
-
-    def __getattr__(self, name):
-        fn = getattr(library(), "snowhost_" + name[len("lgar_"):])
-        return lambda *args: fn(*args[:-1])
+            gp, gta, gpar, gstate = out(True, T, B), out(want_ta, T, B), out(want_par, 7, B), out(want_state, 2, B)
+            calls.append((1, (T, B), (dt_h,), (f64(gw), f64(gice), f64(gliq), f64(p), f64(ta), f64(ice), f64(liq), f64(par), f64(state),
+                                               gp, gta, gpar, gstate)))
+            results.append((gp, gta, gpar, gstate))
+    UNIT.run_calls(calls, sanitize)
+    return [_hostbuild.values(r) for r in results]
 
 
 class SimCatchmentSnow(CatchmentSnow):
@@ -306,4 +256,4 @@ class SimCatchmentSnow(CatchmentSnow):
 
     @classmethod
     def _open(cls, device):
-        return _SnowLibrary()
+        return _hostbuild.AsHipLibrary(("", "snowhost", library))
