@@ -271,6 +271,21 @@ int32_t lgar_forward_tangent_window(const LgarDims *dims, const LgarParams *para
                                     const LgarTangentWindow *window, void *grad_out, void *tangent_runoff, int32_t *status,
                                     int32_t dtype, void *stream, uint32_t *tickets);
 
+/* The tangent along a direction of the FORCING as well: lgar_forward_tangent_window whose step t runs on (precip, precip') and
+ * (pet, pet').  `dforcing` holds the two tangents: its precip / pet are arrays [n_steps][Nf][G] of dtype, G = forcing_group
+ * (LgarDims) and Nf the number of forcing columns, either may be NULL = zeros; column c reads element
+ * (t * Nf + cf) * G + c mod G, cf being the forcing column it reads its values from (by the layout or by
+ * forcing->column_map).  So every lane of a direction group has a forcing tangent of its own (lanes that carry a parameter
+ * direction read zeros), and with Nf = n_columns / G the read is t * n_columns + c.  A forcing direction changes no value:
+ * the W columns of a tangent_share group still hold one value state.  With both tangents NULL or all zero every result has
+ * the bits of lgar_forward_tangent_window.  Everything else -- window (a block of NULLs: fresh state), weights, tickets,
+ * dtype, layer counts, the front-capacity chain -- is lgar_forward_tangent_window's.
+ * LGAR_E_ARG: everything lgar_forward_tangent_window refuses; a null dforcing; a non-null dforcing->column_map. */
+int32_t lgar_forward_tangent_forced(const LgarDims *dims, const LgarParams *params, const LgarParams *direction,
+                                    const LgarForcing *forcing, const LgarForcing *dforcing, const void *w_runoff,
+                                    const void *w_perc, const LgarTangentWindow *window, void *grad_out, void *tangent_runoff,
+                                    int32_t *status, int32_t dtype, void *stream, uint32_t *tickets);
+
 /* Soil-moisture output: the water the front table holds in depth bins (the product the reference reserves and never fills:
  * GlobalParams.soil_moisture_wetting_fronts, physics/GlobalParams.py:61; LGAR-C's soil_moisture_layers).  The theta profile
  * implied by a front table is piecewise constant: front j (depth d_j, water content theta_j, layer tag k_j) reaches up to
@@ -761,6 +776,20 @@ int32_t lgar_catchment_snow_grad(const double *gw, const double *gice, const dou
                                  const double *ice, const double *liq, int32_t n_rows, int32_t n_cells, const double *par,
                                  double dt_h, const double *state_in, double *gp, double *gta, double *gpar, double *gstate,
                                  void *stream);
+
+/* Forward-mode tangent of lgar_catchment_snow along n_dirs = D directions at once: one lane per (cell, direction), everything
+ * fp64.  p, ta, par, dt_h, state_in are the forward's; the value recurrence is the forward's own, so every decision has its
+ * bits.  Input tangents, NULL = zeros: dp, dta [D][n_rows][n_cells]; dpar [D][7][n_cells]; dstate_in [D][2][n_cells].
+ * Outputs: dw(t, b, k) = d w[t][b] along direction k, stored at dw[(t * n_cells + b) * ld + k0 + k] with ld >= k0 + D, so the
+ * call writes straight into the [n_steps][Nf][G] block of forcing tangents lgar_forward_tangent_forced reads (G = ld); the other
+ * elements of a row of ld are not touched.  Optional dice, dliq [D][n_rows][n_cells] (both or neither) and dstate_out
+ * [D][2][n_cells].  Ties go where the forward's selects send them (the adjoint's conventions); n_rows = 0 copies dstate.
+ * lgar_snow.hpp has the recurrence.  Refused with LGAR_E_ARG: negative sizes or k0, ld < k0 + D, a dt_h that is not finite or
+ * <= 0, exactly one of dice / dliq, and (n_rows, n_cells, D > 0) a null p, ta, par or dw. */
+int32_t lgar_catchment_snow_tangent(const double *p, const double *ta, int32_t n_rows, int32_t n_cells, const double *par, double dt_h,
+                                    const double *state_in, int32_t n_dirs, const double *dp, const double *dta, const double *dpar,
+                                    const double *dstate_in, double *dw, int32_t ld, int32_t k0, double *dice, double *dliq,
+                                    double *dstate_out, void *stream);
 
 /* Run totals of a run cut into several lgar_forward calls.  lgar_forward sums a call's accumulators step by step from zero
  * and adds that sum to LgarState.totals, so a chunked run adds several partial sums where one call adds one: the same numbers in

@@ -30,9 +30,9 @@ ST_NAN, ST_NEGBASE, ST_THETA_ORDER, ST_OVERFLOW, ST_ITERCAP, ST_BOTTOM, ST_STRUC
 STATUS_NAMES = {1: "NaN", 2: "negative pow base", 4: "theta order", 8: "front overflow", 16: "iteration cap",
                 32: "front reached domain bottom", 64: "structural error"}
 ABI_VERSION = 4  # LGAR_ABI_VERSION of include/lgar.h this binding mirrors
-EXPORTS = ["lgar_version", "lgar_abi_version", "lgar_sizeof_dims", "lgar_fmax", "lgar_lmax", "lgar_cooperating_lanes", "lgar_state_init", "lgar_forward", "lgar_forward_tangent", "lgar_forward_tangent_window",
+EXPORTS = ["lgar_version", "lgar_abi_version", "lgar_sizeof_dims", "lgar_fmax", "lgar_lmax", "lgar_cooperating_lanes", "lgar_state_init", "lgar_forward", "lgar_forward_tangent", "lgar_forward_tangent_window", "lgar_forward_tangent_forced",
            "lgar_soil_moisture", "lgar_totals_replay", "lgar_catchment_sums", "lgar_catchment_spread", "lgar_catchment_route", "lgar_catchment_route_grad",
-           "lgar_catchment_moments_workspace", "lgar_catchment_moments", "lgar_catchment_moments_grad", "lgar_network_route", "lgar_network_route_grad", "lgar_network_route_mc", "lgar_network_route_mc_grad", "lgar_network_route_pool", "lgar_network_route_pool_grad", "lgar_catchment_baseflow", "lgar_catchment_baseflow_grad", "lgar_catchment_snow", "lgar_catchment_snow_grad", "lgar_leaf_batch", "lgar_leaf_tangent_batch", "lgar_valu_probe", "lgar_valu_probe_insts"]
+           "lgar_catchment_moments_workspace", "lgar_catchment_moments", "lgar_catchment_moments_grad", "lgar_network_route", "lgar_network_route_grad", "lgar_network_route_mc", "lgar_network_route_mc_grad", "lgar_network_route_pool", "lgar_network_route_pool_grad", "lgar_catchment_baseflow", "lgar_catchment_baseflow_grad", "lgar_catchment_snow", "lgar_catchment_snow_grad", "lgar_catchment_snow_tangent", "lgar_leaf_batch", "lgar_leaf_tangent_batch", "lgar_valu_probe", "lgar_valu_probe_insts"]
 
 
 class LgarDims(C.Structure):
@@ -141,6 +141,10 @@ def load():
         lib.lgar_forward_tangent_window.restype = i32
         lib.lgar_forward_tangent_window.argtypes = [p(LgarDims), p(LgarParams), p(LgarParams), p(LgarForcing), vp, vp,
                                                     p(LgarTangentWindow), vp, vp, vp, i32, vp, vp]
+    if hasattr(lib, "lgar_forward_tangent_forced") or not os.environ.get("LGAR_LIB"):  # (a library selected by hand may predate it)
+        lib.lgar_forward_tangent_forced.restype = i32
+        lib.lgar_forward_tangent_forced.argtypes = [p(LgarDims), p(LgarParams), p(LgarParams), p(LgarForcing), p(LgarForcing), vp, vp,
+                                                    p(LgarTangentWindow), vp, vp, vp, i32, vp, vp]
     if hasattr(lib, "lgar_soil_moisture") or not os.environ.get("LGAR_LIB"):  # (a measurement variant built before it existed)
         lib.lgar_soil_moisture.restype = i32
         lib.lgar_soil_moisture.argtypes = [p(LgarDims), p(LgarParams), p(LgarState), vp, i32, i32, vp, vp, vp, i32, vp]
@@ -189,6 +193,9 @@ def load():
         lib.lgar_catchment_snow.argtypes = [vp, vp, i32, i32, vp, dbl, vp, vp, vp, vp, vp, vp]
         lib.lgar_catchment_snow_grad.restype = i32
         lib.lgar_catchment_snow_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, dbl, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "lgar_catchment_snow_tangent") or not os.environ.get("LGAR_LIB"):  # (a library selected by hand may predate it)
+        lib.lgar_catchment_snow_tangent.restype = i32
+        lib.lgar_catchment_snow_tangent.argtypes = [vp, vp, i32, i32, vp, dbl, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
     lib.lgar_leaf_batch.restype = i32
     lib.lgar_leaf_batch.argtypes = [i32, i32, vp, vp, dbl, vp, vp, vp, vp, vp, i32, dbl, vp, i32, vp]
     if hasattr(lib, "lgar_leaf_tangent_batch") or not os.environ.get("LGAR_LIB"):  # (a library selected by hand may predate it)

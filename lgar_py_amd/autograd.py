@@ -15,7 +15,9 @@ import weakref
 import torch
 
 from ._capi import ST_FAULT_MASK
+from .catchments import CatchmentMap
 from .engine import LgarEngine, LgarError, LgarStatusError
+from .forcing import ForcingDirections
 
 KINDS = ("alpha", "n", "ksat")
 # the directions of a backward pass ride side by side as extra columns of a tangent launch (column-major: column
@@ -26,7 +28,21 @@ BATCH_DIRECTIONS_MAX_COLUMNS = 1 << 23
 SHARE_MIN_LANES = 65536  # columns x directions: one wave on every SIMD of the chip
 
 
-def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcing_map=None, start=None):
+def _forcing_lanes(fd, part, T, Nf, dtype, device):
+    """The forcing tangents of one group of directions: {} when `part` holds no ("forcing", k), else d_precip / d_pet
+    [T, Nf, len(part)] with fd's series k in the lane of ("forcing", k) and zeros in the lanes of the parameter directions."""
+    lanes = [(b, key[1]) for b, key in enumerate(part) if key[0] == "forcing"]
+    out = {}
+    for nm, src in (("d_precip", fd.d_precip), ("d_pet", fd.d_pet)) if lanes else ():
+        if src is not None:
+            d = torch.zeros(T, Nf, len(part), dtype=dtype, device=device)
+            for b, k in lanes:
+                d[:, :, b] = src[k].to(device, dtype)
+            out[nm] = d
+    return out
+
+
+def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcing_map=None, start=None, forcing_directions=None):
     """Vector-Jacobian product for every (kind, layer) in `wanted` (list of (kind, l)).
     Returns ({(kind, l): grad[N]}, tangent_status[N]).  Columns are independent, so the directions are laid side by side as
     len(wanted) * N columns of a single launch (fills the chip even for ensembles of 10^5 columns; very large jobs go in
@@ -37,8 +53,14 @@ def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcin
     start: None = the run starts from a fresh state; an engine.EngineState (LgarEngine.snapshot()) = the rows are a window that
     starts from that FIXED state (LgarEngine.tangent_window: the derivative of forward() from the state, nothing flows into the
     run that produced it).  Where the directions ride side by side the state is laid out with them (repeat_interleave: (5 F +
-    NSCAL) * Dg * N values, small beside the [T, N] arrays)."""
+    NSCAL) * Dg * N values, small beside the [T, N] arrays).
+    forcing_directions: a forcing.ForcingDirections over the run's forcing columns; `wanted` may then hold ("forcing", k) as
+    well: lane k of a column integrates the forcing tangent d_precip[k] / d_pet[k] of the column's forcing cell
+    (lgar_forward_tangent_forced) and the result is the column's own share of d loss / d params[k] of its cell.  Groups without
+    such a lane are launched as they always were."""
     L, N, D = eng.L, eng.N, len(wanted)
+    fd = forcing_directions
+    T, Nf = (int(precip.shape[0]), int(precip.shape[1])) if fd is not None else (0, 0)
     out = {}
     status = torch.zeros(N, dtype=torch.int32, device=eng.device)
     if D == 0:
@@ -56,13 +78,17 @@ def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcin
         Dg = len(part)
         if Dg == 1:
             kind, l = part[0]
-            dmat = torch.zeros(L, N, dtype=eng.dtype, device=eng.device)
-            dmat[l] = 1.0
-            if start is None:
-                out[(kind, l)], _, st = eng.tangent({kind: dmat}, precip, pet, w_runoff=w_runoff, w_perc=w_perc, forcing_map=forcing_map)
+            if kind == "forcing":
+                direction, fkw = {}, _forcing_lanes(fd, part, T, Nf, eng.dtype, eng.device)
             else:
-                out[(kind, l)], _, st, _ = eng.tangent_window({kind: dmat}, precip, pet, w_runoff=w_runoff, w_perc=w_perc,
-                                                              forcing_map=forcing_map, start=start, keep_state=False)
+                dmat = torch.zeros(L, N, dtype=eng.dtype, device=eng.device)
+                dmat[l] = 1.0
+                direction, fkw = {kind: dmat}, {}
+            if start is None:
+                out[(kind, l)], _, st = eng.tangent(direction, precip, pet, w_runoff=w_runoff, w_perc=w_perc, forcing_map=forcing_map, **fkw)
+            else:
+                out[(kind, l)], _, st, _ = eng.tangent_window(direction, precip, pet, w_runoff=w_runoff, w_perc=w_perc,
+                                                              forcing_map=forcing_map, start=start, keep_state=False, **fkw)
             status |= st
             continue
         # column n's Dg directions sit in ADJACENT lanes (column n * Dg + b): they follow the same branches, so a wavefront
@@ -72,10 +98,12 @@ def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcin
                        with_state=False)
         dirs = {k: torch.zeros(L, Dg * N, dtype=eng.dtype, device=eng.device) for k in KINDS}
         for b, (kind, l) in enumerate(part):
-            dirs[kind][l, b::Dg] = 1.0
+            if kind != "forcing":
+                dirs[kind][l, b::Dg] = 1.0
         # forcing / weights broadcast by the kernel (forcing_group); the SAME map, not replicated: entry c // Dg of the launch is
         # the original column, and the incoming [T, N] gradient is the [T, Dg * N // Dg] weight array as it is
         kw = dict(w_runoff=w_runoff, w_perc=w_perc, forcing_group=Dg, share=Dg if share else 0, forcing_map=forcing_map)
+        kw.update(_forcing_lanes(fd, part, T, Nf, eng.dtype, eng.device))
         if start is None:
             g, _, st = big.tangent(dirs, precip, pet, **kw)
         else:
@@ -97,11 +125,12 @@ def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcin
 
 class LgarSeriesFunction(torch.autograd.Function):
     """(alpha, n, ksat)[L, N] -> (runoff, percolation)[T, N] from a fresh state, or from a given one held fixed; differentiable
-    in alpha/n/ksat."""
+    in alpha/n/ksat and, through forcing_directions, in the parameters the forcing was computed from (the inputs behind engine_kw)."""
 
     @staticmethod
-    def forward(ctx, alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, engine_kw):
+    def forward(ctx, alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, engine_kw, *forcing_params):
         engine_kw = dict(engine_kw)
+        fd = engine_kw.pop("forcing_directions", None)
         check = engine_kw.pop("check", True)
         status_out = engine_kw.pop("status_out", None)
         fmap = engine_kw.pop("forcing_map", None)
@@ -109,6 +138,9 @@ class LgarSeriesFunction(torch.autograd.Function):
         state_out = engine_kw.pop("state_out", None)
         eng = LgarEngine(alpha.detach(), n.detach(), ksat.detach(), theta_e, theta_r, thickness, **engine_kw)
         precip, pet = torch.as_tensor(precip), torch.as_tensor(pet)
+        if fd is not None and fmap is None and (precip.dim() != 2 or precip.shape[1] != eng.N):
+            raise LgarError("forcing_directions need [T, N] forcing or a forcing_map, not the broadcast [T, Nf] layout: a forcing "
+                            "cell there is read by columns that are not one group, and its parameters' lanes have no place")
         if fmap is not None:
             pass  # [T, B] forcing through the map, forward and backward: nothing is expanded (the weights do not go through it)
         elif precip.dim() == 2 and precip.shape[1] != eng.N:
@@ -119,6 +151,10 @@ class LgarSeriesFunction(torch.autograd.Function):
                                 % (eng.N, tuple(precip.shape), tuple(pet.shape)))
             rep = eng.N // int(precip.shape[1])
             precip, pet = precip.repeat(1, rep).contiguous(), pet.repeat(1, rep).contiguous()  # column c reads c % Nf
+        if fd is not None:
+            if fd.K and fd.shape != (fd.K, int(precip.shape[0]), int(precip.shape[1])):
+                raise LgarError("forcing_directions hold %s, the forcing is [T, B] = %s: d_precip / d_pet must be [K, T, B]"
+                                % (fd.shape, tuple(precip.shape)))
         if start is not None:
             eng.restore(start)  # (in place of the fresh state the constructor left)
         out = eng.forward(precip, pet, series=("runoff", "percolation"), check=check, forcing_map=fmap)
@@ -130,6 +166,7 @@ class LgarSeriesFunction(torch.autograd.Function):
         ctx.forcing = (precip, pet)
         ctx.forcing_map = fmap
         ctx.start = start
+        ctx.forcing_directions = fd
         ctx.in_dtypes = (alpha.dtype, n.dtype, ksat.dtype)
         ctx.check = check
         ctx.status_out = status_out
@@ -145,7 +182,11 @@ class LgarSeriesFunction(torch.autograd.Function):
         keep = (~fwd_bad).to(g_runoff.dtype)[None, :] if g_runoff is not None else None
         gr = None if g_runoff is None else g_runoff * keep
         gp = None if g_perc is None else g_perc * ((~fwd_bad).to(g_perc.dtype)[None, :])
-        vj, st = parameter_vjp(eng, precip, pet, gr, gp, wanted, check=False, forcing_map=ctx.forcing_map, start=ctx.start)
+        fd = ctx.forcing_directions
+        # the forcing's parameters ride as K more lanes per column in the same groups: one batch of launches
+        wanted += [("forcing", k) for k in range(fd.K if fd is not None else 0) if ctx.needs_input_grad[9 + k]]
+        vj, st = parameter_vjp(eng, precip, pet, gr, gp, wanted, check=False, forcing_map=ctx.forcing_map, start=ctx.start,
+                               forcing_directions=fd)
         st = torch.where(fwd_bad, torch.zeros_like(st), st)
         if ctx.status_out is not None:
             ctx.status_out.append(st)  # [forward status, tangent status]
@@ -159,7 +200,29 @@ class LgarSeriesFunction(torch.autograd.Function):
             g = torch.stack([vj[(kind, l)] for l in range(eng.L)])
             g = torch.where(fwd_bad[None, :], torch.zeros_like(g), g)
             grads.append(g.to(ctx.in_dtypes[ki]))
-        return (*grads, None, None, None, None, None, None)
+        return (*grads, None, None, None, None, None, None, *_forcing_parameter_grads(ctx, fd, vj, fwd_bad))
+
+
+def _forcing_parameter_grads(ctx, fd, vj, fwd_bad):
+    """d loss / d params[k] of a ForcingDirections from the columns' shares vj[("forcing", k)] [N]: with a forcing_map the columns
+    of a cell are summed in the fixed order of CatchmentMap.sums (its bits, whatever the launch), with [T, N] forcing a column is
+    its own cell; a scalar parameter gets the sum over the cells."""
+    if fd is None:
+        return ()
+    eng = ctx.engine
+    ks = [k for k in range(fd.K) if ctx.needs_input_grad[9 + k]]
+    cells = {}
+    if ks:
+        shares = torch.stack([torch.where(fwd_bad, torch.zeros_like(vj[("forcing", k)]), vj[("forcing", k)]) for k in ks])
+        shares = shares.to(torch.float64).contiguous()
+        if ctx.forcing_map is not None:
+            shares = ctx.forcing_map.cell_map(CatchmentMap).sums(shares)  # (the map of the cells is made once per ForcingMap)
+        cells = dict(zip(ks, shares))
+    out = []
+    for k, p in enumerate(fd.params):
+        g = cells.get(k)
+        out.append(None if g is None else (g.sum() if p.dim() == 0 else g).to(p.device, p.dtype))
+    return tuple(out)
 
 
 def lgar_series(alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, **engine_kw):
@@ -173,8 +236,18 @@ def lgar_series(alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, **engi
     the run from the fixed state over these rows.  Nothing flows into the spin-up that produced the state, although that spin-up
     depended on the same parameters -- the usual "warm-up excluded from the gradient".  The backward pass integrates the tangent
     over these rows only.  state_out=[]: the forward pass appends the end state (an EngineState), which the next window takes as
-    its initial_state.  initial_state=None is a run from a fresh state."""
-    return LgarSeriesFunction.apply(alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, engine_kw)
+    its initial_state.  initial_state=None is a run from a fresh state.
+    forcing_directions=<forcing.ForcingDirections> (forcing.scaled_forcing, snow.catchment_snow_directions): the forcing was
+    computed from K parameters per forcing cell and fd holds its derivatives along them; fd.params become inputs of the node and
+    receive d loss / d params[k] ([B], or the sum over the cells for a scalar), from K more lanes per column in the backward
+    pass's launches.  The forcing must be [T, N] or go through a forcing_map (the broadcast [T, Nf] layout raises LgarError); it
+    works with initial_state.  The graph of `precip` / `pet` themselves is NOT followed: they are constants to this node, and
+    whatever produced them receives a gradient through forcing_directions or not at all.  Without forcing_directions the
+    backward pass is what it was, launch for launch."""
+    fd = engine_kw.get("forcing_directions")
+    if fd is not None and not isinstance(fd, ForcingDirections):
+        raise LgarError("forcing_directions must be a forcing.ForcingDirections; got %s" % type(fd).__name__)
+    return LgarSeriesFunction.apply(alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, engine_kw, *(fd.params if fd is not None else ()))
 
 
 class _ChunkFunction(torch.autograd.Function):

@@ -16,8 +16,10 @@ UNITS = [("lgar_kernels.hip", [], ""), ("lgar_probe.hip", [], ""), ("lgar_moistu
          ("lgar_network_mc.hip", [], ""), ("lgar_network_pool.hip", [], ""), ("lgar_snow.hip", [], ""),
          ("lgar_leaf_tangent.hip", [], "")] + \
         [("lgar_kernels_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS] + \
-        [("lgar_tangent_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS]
-TANGENT_SOURCES = ("lgar_tangent_nl.hip",)  # what a build without the tangent leaves out (both tangent kernel families)
+        [("lgar_tangent_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS] + \
+        [("lgar_tangent_forced_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS]
+# what a build without the tangent leaves out (all three tangent kernel families)
+TANGENT_SOURCES = ("lgar_tangent_nl.hip", "lgar_tangent_forced_nl.hip")
 SOURCES = sorted(set(u[0] for u in UNITS))
 # every header the units may include (taken from the directory: a header left off a hand-kept list would let a stale library
 # be reused after it changed)

@@ -205,6 +205,22 @@ int32_t lgar_forward_tangent_window(const LgarDims *dims, const LgarParams *para
                                                          tangent_runoff, status, dtype, (hipStream_t)stream, tickets);
   });
 }
+
+int32_t lgar_forward_tangent_forced(const LgarDims *dims, const LgarParams *params, const LgarParams *direction,
+                                    const LgarForcing *forcing, const LgarForcing *dforcing, const void *w_runoff,
+                                    const void *w_perc, const LgarTangentWindow *window, void *grad_out, void *tangent_runoff,
+                                    int32_t *status, int32_t dtype, void *stream, uint32_t *tickets) {
+  int rc = check_tangent_call(dims, params, direction, forcing, grad_out, status);
+  if (rc) return rc;
+  rc = check_window(window);
+  if (rc) return rc;
+  rc = check_forcing_direction(dforcing);
+  if (rc) return rc;
+  return by_layers(dims->n_layers, [&](auto nl) {
+    return launch_tangent_forced_nl<decltype(nl)::value>(dims, params, direction, forcing, dforcing, w_runoff, w_perc, window,
+                                                         grad_out, tangent_runoff, status, dtype, (hipStream_t)stream, tickets);
+  });
+}
 #endif
 
 int32_t lgar_soil_moisture(const LgarDims *dims, const LgarParams *params, const LgarState *state, const double *edges,

@@ -107,6 +107,13 @@ inline int check_window(const LgarTangentWindow *w) {
   return 0;
 }
 
+// What lgar_forward_tangent_forced refuses beyond that: the forcing tangents have the layout [n_steps][Nf][forcing_group], which
+// the forcing's own column (layout or column_map) already indexes; a map of their own has no meaning.
+inline int check_forcing_direction(const LgarForcing *df) {
+  if (!df || df->column_map != nullptr) return LGAR_E_ARG;
+  return 0;
+}
+
 // The forward / init kernels' argument block of one call: one kernel on its own, no work counter, one lane per column (the
 // launchers set ticket and coop; chain_step the position in a chain).
 template <typename R>

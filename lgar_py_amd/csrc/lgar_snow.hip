@@ -21,6 +21,12 @@ template <bool GP> __global__ __launch_bounds__(256) void lgar_snow_grad_kernel(
   for (long long b = (long long)blockIdx.x * 256 + threadIdx.x; b < a.B; b += (long long)gridDim.x * 256) sn_walk_back<GP>(a, b);
 }
 
+// one lane per (cell, direction): lane i = k * B + b
+__global__ __launch_bounds__(256) void lgar_snow_tangent_kernel(SnTanArgs a) {
+  const long long n = a.B * a.D;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) sn_walk_tangent(a, i % a.B, i / a.B);
+}
+
 static dim3 sn_grid(long long B) {
   const long long blocks = (B + 255) / 256;
   return dim3((unsigned)(blocks < LGAR_SN_GRID_CAP ? blocks : LGAR_SN_GRID_CAP));
@@ -28,6 +34,11 @@ static dim3 sn_grid(long long B) {
 
 int launch_snow(const SnArgs &a, hipStream_t stream) {
   hipLaunchKernelGGL(lgar_snow_kernel, sn_grid(a.B), dim3(256), 0, stream, a);
+  return launch_status();
+}
+
+int launch_snow_tangent(const SnTanArgs &a, hipStream_t stream) {
+  hipLaunchKernelGGL(lgar_snow_tangent_kernel, sn_grid(a.B * a.D), dim3(256), 0, stream, a);
   return launch_status();
 }
 
@@ -64,6 +75,19 @@ int32_t lgar_catchment_snow_grad(const double *gw, const double *gice, const dou
   a.gp = gp, a.gta = gta, a.gpar = gpar, a.gstate = gstate;
   a.dt_h = dt_h, a.T = n_rows, a.B = n_cells;
   return lgar::launch_snow_grad(a, (hipStream_t)stream);
+}
+
+int32_t lgar_catchment_snow_tangent(const double *p, const double *ta, int32_t n_rows, int32_t n_cells, const double *par, double dt_h,
+                                    const double *state_in, int32_t n_dirs, const double *dp, const double *dta, const double *dpar,
+                                    const double *dstate_in, double *dw, int32_t ld, int32_t k0, double *dice, double *dliq,
+                                    double *dstate_out, void *stream) {
+  const int rc = lgar::sn_tangent_check(p, ta, n_rows, n_cells, par, dt_h, n_dirs, dw, ld, k0, dice, dliq, dstate_out);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  lgar::SnTanArgs a;
+  a.p = p, a.ta = ta, a.par = par, a.state_in = state_in, a.dp = dp, a.dta = dta, a.dpar = dpar, a.dstate_in = dstate_in;
+  a.dw = dw, a.dice = dice, a.dliq = dliq, a.dstate_out = dstate_out;
+  a.dt_h = dt_h, a.T = n_rows, a.B = n_cells, a.D = n_dirs, a.ld = ld, a.k0 = k0;
+  return lgar::launch_snow_tangent(a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -259,6 +259,114 @@ template <bool GP> LGAR_SN_FN void sn_walk_back(const SnGradArgs &a, long long b
   }
 }
 
+// ---- the forward-mode tangent (lgar_catchment_snow_tangent) ----------------------------------------------
+// One lane per (cell b, direction k), k < D: lane i = k * B + b, cell fastest, so the loads of dp / dta [D][T][B] and of the values
+// are coalesced.  The VALUE recurrence of the lane is sn_step itself from state_in (every flag has the forward's bits); beside it
+// run ice', liq' from dstate_in (NULL: +0.0).  Once per lane, with tlo' .. cwh' = dpar[k][0..6][b] (NULL: 0):
+//     cd' = cfmax' * dt_h;   cr' = cfr' * cd + cfr * cd';   span' = thi' - tlo'
+// and per row, selects on the forward's flags with the adjoint's tie conventions (mid = !lo && !hi):
+//     pd'   = dp * dt_h
+//     fr'   = mid ? ((Ta' - tlo') - fr * span') / span : 0.0        (the quotient formed for every lane, then selected)
+//     rain' = pd' * fr + pd * fr';   dry' = pd' - rain';   snow' = sfcf' * dry + sfcf * dry'
+//     d'    = Ta' - tm';             ice1' = ice' + snow'
+//     pm'   = cd' * d + cd * d';     melt' = warm ? (ml ? ice1' : pm') : 0.0
+//     pr'   = cr' * (-d) - cr * d';  refr' = warm ? 0.0 : (rl ? liq' : pr')
+//     ice2' = (ice1' - melt') + refr';   liq1' = ((liq' + rain') + melt') - refr'
+//     cap'  = cwh' * ice2 + cwh * ice2'; out' = over ? liq1' - cap' : 0.0
+//     liq'  = over ? cap' : liq1';       ice' = ice2'
+//     dw[(t * B + b) * ld + k0 + k] = out' / dt_h;   dice[k][t][b] = ice';   dliq[k][t][b] = liq'
+// ld >= k0 + D: the lane writes straight into the [T][B][G] block of forcing tangents lgar_forward_tangent_forced reads.  T = 0
+// copies dstate.  Rows in chunks of LGAR_SN_CHUNK as the forward walk; no fma, IEEE divisions.
+struct SnTanArgs {
+  const double *p, *ta, *par, *state_in;      // the forward's inputs
+  const double *dp, *dta, *dpar, *dstate_in;  // [D][T][B], [D][T][B], [D][7][B], [D][2][B]; NULL: zeros
+  double *dw, *dice, *dliq, *dstate_out;      // dw [T][B][ld] at k0 + k; dice, dliq [D][T][B] (both or neither); dstate_out [D][2][B]
+  double dt_h;
+  long long T, B, D, ld, k0;
+};
+
+LGAR_SN_FN void sn_walk_tangent(const SnTanArgs &a, long long b, long long k) {
+  constexpr int CH = LGAR_SN_CHUNK;
+  const long long TB = a.T * a.B;
+  double ice = a.state_in ? a.state_in[b] : 0.0, liq = a.state_in ? a.state_in[a.B + b] : 0.0;
+  double dice = a.dstate_in ? a.dstate_in[(k * 2 + 0) * a.B + b] : 0.0, dliq = a.dstate_in ? a.dstate_in[(k * 2 + 1) * a.B + b] : 0.0;
+  if (a.T > 0) {
+    const SnPar c = sn_par(a.par, a.B, b, a.dt_h);
+    const double *dq = a.dpar ? a.dpar + k * LGAR_SN_NPAR * a.B + b : nullptr;
+    const double dtlo = dq ? dq[0] : 0.0, dthi = dq ? dq[a.B] : 0.0, dtm = dq ? dq[2 * a.B] : 0.0, dsfcf = dq ? dq[3 * a.B] : 0.0;
+    const double dcfmax = dq ? dq[4 * a.B] : 0.0, dcfr = dq ? dq[5 * a.B] : 0.0, dcwh = dq ? dq[6 * a.B] : 0.0;
+    const double dcd = dcfmax * a.dt_h;
+    const double dcr = dcfr * c.cd + c.cfr * dcd;
+    const double dspan = dthi - dtlo;
+    for (long long t0 = 0; t0 < a.T; t0 += CH) {
+      double pv[CH], tv[CH], dpv[CH], dtv[CH];
+#pragma unroll
+      for (int u = 0; u < CH; u++) pv[u] = a.p[sn_row<1>(t0, u, a.T) * a.B + b];
+#pragma unroll
+      for (int u = 0; u < CH; u++) tv[u] = a.ta[sn_row<1>(t0, u, a.T) * a.B + b];
+#pragma unroll
+      for (int u = 0; u < CH; u++) dpv[u] = a.dp ? a.dp[k * TB + sn_row<1>(t0, u, a.T) * a.B + b] : 0.0;
+#pragma unroll
+      for (int u = 0; u < CH; u++) dtv[u] = a.dta ? a.dta[k * TB + sn_row<1>(t0, u, a.T) * a.B + b] : 0.0;
+#pragma unroll
+      for (int u = 0; u < CH; u++)
+        if (t0 + u < a.T) {
+          const long long t = t0 + u;
+          const double pd = pv[u] * a.dt_h;
+          const SnRow o = sn_step(ice, liq, pd, tv[u], c);
+          const bool mid = !o.lo && !o.hi;
+          const double dpd = dpv[u] * a.dt_h;
+          const double q = ((dtv[u] - dtlo) - o.fr * dspan) / c.span;  // formed for every lane, then selected
+          const double dfr = mid ? q : 0.0;
+          const double drain = dpd * o.fr + pd * dfr;
+          const double ddry = dpd - drain;
+          const double dsnow = dsfcf * o.dry + c.sfcf * ddry;
+          const double dd = dtv[u] - dtm;
+          const double dice1 = dice + dsnow;
+          const double dpm = dcd * o.d + c.cd * dd;
+          const double dmelt = o.warm ? (o.ml ? dice1 : dpm) : 0.0;
+          const double dpr = dcr * (-o.d) - c.cr * dd;
+          const double drefr = o.warm ? 0.0 : (o.rl ? dliq : dpr);
+          const double dice2 = (dice1 - dmelt) + drefr;
+          const double dliq1 = ((dliq + drain) + dmelt) - drefr;
+          const double dcap = dcwh * o.ice2 + c.cwh * dice2;
+          const double dout = o.over ? dliq1 - dcap : 0.0;
+          dliq = o.over ? dcap : dliq1;
+          dice = dice2;
+          ice = o.ice, liq = o.liq;
+          a.dw[(t * a.B + b) * a.ld + a.k0 + k] = dout / a.dt_h;
+          if (a.dice) {
+            a.dice[k * TB + t * a.B + b] = dice;
+            a.dliq[k * TB + t * a.B + b] = dliq;
+          }
+        }
+    }
+  }
+  if (a.dstate_out) {
+    a.dstate_out[(k * 2 + 0) * a.B + b] = dice;
+    a.dstate_out[(k * 2 + 1) * a.B + b] = dliq;
+  }
+}
+
+// 0: launch; 1: nothing to do; LGAR_E_ARG
+inline int sn_tangent_check(const double *p, const double *ta, int32_t T, int32_t B, const double *par, double dt_h, int32_t D,
+                            const double *dw, int32_t ld, int32_t k0, const double *dice, const double *dliq, const double *dstate_out) {
+  if (T < 0 || B < 0 || D < 0 || k0 < 0 || !(dt_h > 0.0 && dt_h <= 1.7976931348623157e308)) return LGAR_E_ARG;
+  if ((dice == nullptr) != (dliq == nullptr)) return LGAR_E_ARG;
+  if ((long long)ld < (long long)k0 + (long long)D) return LGAR_E_ARG;
+  if (B == 0 || D == 0) return 1;
+  if (T == 0) return dstate_out ? 0 : 1;
+  if (!p || !ta || !par || !dw) return LGAR_E_ARG;
+  return 0;
+}
+
+#ifdef LGAR_DEVSIM
+inline void sn_tangent_all(const SnTanArgs &a) {
+  for (long long k = 0; k < a.D; k++)
+    for (long long b = 0; b < a.B; b++) sn_walk_tangent(a, b, k);
+}
+#endif
+
 // ---- what the entry points refuse (host code) -------------------------------------------------------------------------------
 inline bool sn_dt_ok(double dt_h) { return dt_h > 0.0 && dt_h <= 1.7976931348623157e308; }  // finite and > 0 (a NaN fails both)
 

@@ -14,6 +14,12 @@
 // state + tangent state (TWindow::in / din) instead of the fresh one, continues the fold of grad from grad_in, and the kernel
 // that FINISHES a column stores both states (TWindow::out / dout).  A handed-over column is redone from in / din / grad_in, which
 // nobody writes.  Everything about the window sits behind `if constexpr (WINDOW)`: the plain instantiations are what they were.
+//
+// Forced kernels (lgar_forward_tangent_forced, lgar_tangent_forced_kernel, lgar_tangent_forced_nl.hip): tangent_lane<..., WINDOW =
+// true, FORCED = true> is the window lane whose forcing is a dual number too: step t runs forward(S(precip, dprecip), S(pet,
+// dpet)) with the two tangents read from TForcing ([T][Nf][Fg]: every lane of a direction group has its own).  A forcing
+// direction changes no value, so tangent_share, the capacity chain and the window are the window family's.  Everything about
+// it sits behind `if constexpr (FORCED)`.
 #pragma once
 #include <type_traits>
 
@@ -58,6 +64,16 @@ template <typename R> struct TWindow {
 template <typename R> struct TWArgs {
   TArgs<R> a;
   TWindow<R> w;
+};
+
+// the forcing tangents of one lgar_forward_tangent_forced call; it follows the window block in the forced kernels' argument block
+template <typename R> struct TForcing {
+  const R *dprecip, *dpet;  // [T][Nf][Fg] or null = zeros: column c reads (t * Nf + cf) * Fg + c % Fg, cf its forcing column
+};
+template <typename R> struct TFArgs {
+  TArgs<R> a;
+  TWindow<R> w;
+  TForcing<R> f;
 };
 
 template <typename Q, typename B, typename I> inline TStateP<Q, B, I> make_tstate(const LgarState *s) {
@@ -114,9 +130,24 @@ inline TWArgs<R> make_twargs(const LgarDims *d, const LgarParams *p, const LgarP
   return t;
 }
 
-// the TArgs of either argument block: what the launch and the chain write (ticket, chain_step)
+// ... and of one lgar_forward_tangent_forced call
+template <typename R>
+inline TFArgs<R> make_tfargs(const LgarDims *d, const LgarParams *p, const LgarParams *dir, const LgarForcing *f, const LgarForcing *df,
+                             const void *w_runoff, const void *w_perc, const LgarTangentWindow *win, void *grad_out,
+                             void *tangent_runoff, int32_t *status) {
+  const TWArgs<R> tw = make_twargs<R>(d, p, dir, f, w_runoff, w_perc, win, grad_out, tangent_runoff, status);
+  TFArgs<R> t;
+  t.a = tw.a;
+  t.w = tw.w;
+  t.f.dprecip = (const R *)df->precip;
+  t.f.dpet = (const R *)df->pet;
+  return t;
+}
+
+// the TArgs of any argument block: what the launch and the chain write (ticket, chain_step)
 template <typename R> inline TArgs<R> &targs(TArgs<R> &a) { return a; }
 template <typename R> inline TArgs<R> &targs(TWArgs<R> &a) { return a.a; }
+template <typename R> inline TArgs<R> &targs(TFArgs<R> &a) { return a.a; }
 
 // The walk of a tangent plan (lgar_plan.hpp), for both kernel families, the library's launcher and the host builds of the tests
 // alike: kernel i's place in the chain goes into the block, then run(cap, mode, work counter) -- cap and mode as
@@ -137,9 +168,10 @@ template <typename A, typename Run> inline int tangent_chain(A &a, const Tangent
   return 0;
 }
 
-template <typename R, int NL, int FMAX, int MODE, bool WINDOW = false>
+template <typename R, int NL, int FMAX, int MODE, bool WINDOW = false, bool FORCED = false>
 __device__ __forceinline__ void tangent_lane(const LGAR_KARG TArgs<R> *ap, size_t c, int lane, WaveLDS<Dual<R>, FMAX, 1> &lds,
-                                             R *xchg = nullptr, const LGAR_KARG TWindow<R> *wp = nullptr) {
+                                             R *xchg = nullptr, const LGAR_KARG TWindow<R> *wp = nullptr,
+                                             const LGAR_KARG TForcing<R> *fp = nullptr) {
   using S = Dual<R>;
   const LGAR_KARG TArgs<R> &a = *ap;
   const size_t N = (size_t)a.N;
@@ -229,6 +261,18 @@ __device__ __forceinline__ void tangent_lane(const LGAR_KARG TArgs<R> *ap, size_
     if (a.w_runoff) wr_ahead = a.w_runoff[ow];
     if (a.w_perc) wp_ahead = a.w_perc[ow];
   }
+  // FORCED: the forcing's two tangents travel with the values: loaded one step ahead, settled with them, carried as they are.
+  // Their offset is the values' times Fg plus this lane's place in its direction group (with Nf = N / Fg: t * N + c).
+  [[maybe_unused]] R dprecip_ahead = R(0), dpet_ahead = R(0);
+  [[maybe_unused]] size_t cg = 0;
+  if constexpr (FORCED) {
+    cg = (size_t)((unsigned)c % (unsigned)a.Fg);
+    if (a.T > 0) {
+      const size_t od = cf * (size_t)a.Fg + cg;
+      if (fp->dprecip) dprecip_ahead = fp->dprecip[od];
+      if (fp->dpet) dpet_ahead = fp->dpet[od];
+    }
+  }
   for (int t = 0; t < a.T; t++) {
     if constexpr (WINDOW) {
       if (handed_over) break;  // (handed over at load)
@@ -248,7 +292,17 @@ __device__ __forceinline__ void tangent_lane(const LGAR_KARG TArgs<R> *ap, size_
       if (a.w_runoff) wr_ahead = a.w_runoff[ow];
       if (a.w_perc) wp_ahead = a.w_perc[ow];
     }
-    col.forward(S(precip), S(pet));
+    if constexpr (FORCED) {
+      const R dprecip = dprecip_ahead, dpet = dpet_ahead;
+      const size_t tn = (size_t)((t + 1 < a.T) ? t + 1 : t);
+      const size_t od = (tn * Nf + cf) * (size_t)a.Fg + cg;
+      if (fp->dprecip) dprecip_ahead = fp->dprecip[od];
+      if (fp->dpet) dpet_ahead = fp->dpet[od];
+      col.forward(S(precip, dprecip), S(pet, dpet));
+      settle_load(dprecip_ahead); settle_load(dpet_ahead);
+    } else {
+      col.forward(S(precip), S(pet));
+    }
     settle_load(precip_ahead); settle_load(pet_ahead); settle_load(wr_ahead); settle_load(wp_ahead);
     if (a.w_runoff) grad += wr * col.a_runoff.d;
     if (a.w_perc) grad += wp * col.a_perc.d;

@@ -462,22 +462,44 @@ class LgarEngine:
                 raise LgarError("direction[%r] must be [L, N]" % k)
         return precip, pet, w_runoff, w_perc, dirs
 
-    def _tangent_call(self, name, inputs, forcing_map, want_series, window=(), grad=None, st=None):
+    def _forcing_direction(self, d_precip, d_pet, precip):
+        """The forcing tangents of tangent() / tangent_window() on the device in the engine's dtype and checked against the forcing
+        `precip` that _forcing returned: [T, Nf, G] each (G = forcing_group; [T, Nf] will do when G = 1), or None.  Returns the
+        LgarForcing block that holds them and the tensors it points into."""
+        T, Nf, g = precip.shape[0], precip.shape[1], self.dims.forcing_group
+        keep = []
+        for nm, d in (("d_precip", d_precip), ("d_pet", d_pet)):
+            if d is not None:
+                d = torch.as_tensor(d).to(self.device, self.dtype).contiguous()
+                if tuple(d.shape) != (T, Nf, g) and not (g == 1 and tuple(d.shape) == (T, Nf)):
+                    raise LgarError("%s must be [T, Nf, forcing_group] = [%d, %d, %d]: one tangent per lane of a direction group of "
+                                    "each forcing column; got %s" % (nm, T, Nf, g, tuple(d.shape)))
+            keep.append(d)
+        return _capi.LgarForcing(_ptr(keep[0]), _ptr(keep[1]), None), keep
+
+    def _tangent_call(self, name, inputs, forcing_map, want_series, window=(), grad=None, st=None, d_forcing=None):
         """What tangent() and tangent_window() do alike with _tangent_inputs' results: lgar_<name> with the direction and forcing
-        blocks, `window` (the arguments between the weights and grad) and fresh work counters.  Returns (grad, series, st)."""
+        blocks, `window` (the arguments between the weights and grad) and fresh work counters.  d_forcing = (d_precip, d_pet):
+        the call goes to lgar_forward_tangent_forced, with the block of the forcing's tangents behind the forcing.  Returns
+        (grad, series, st)."""
         precip, pet, w_runoff, w_perc, dirs = inputs
         dstruct = _capi.LgarParams(_ptr(dirs["alpha"]), _ptr(dirs["n"]), _ptr(dirs["ksat"]), None, None, None)
         grad = torch.zeros(self.N, dtype=self.dtype, device=self.device) if grad is None else grad
         ser = self._new_series(precip.shape[0], self.N, dtype=self.dtype, device=self.device) if want_series else None
         st = torch.zeros(self.N, dtype=torch.int32, device=self.device) if st is None else st
         tickets = torch.zeros(_capi.NTICKETS, dtype=torch.int32, device=self.device)  # persistent-wave work counters
+        self._last_tickets = tickets  # (for the tests: entries 4, 5 count the columns kernels 0, 1 of the chain handed over)
         fo = _capi.LgarForcing(precip.data_ptr(), pet.data_ptr(), None if forcing_map is None else forcing_map.index.data_ptr())
-        self._call(name, C.byref(self.dims), C.byref(self._params), C.byref(dstruct), C.byref(fo), _ptr(w_runoff), _ptr(w_perc),
-                   *window, grad.data_ptr(), _ptr(ser), st.data_ptr(), counters=tickets)
+        forced = ()
+        if d_forcing is not None:
+            dfo, keep = self._forcing_direction(*d_forcing, precip)
+            name, forced = "forward_tangent_forced", (C.byref(dfo),)
+        self._call(name, C.byref(self.dims), C.byref(self._params), C.byref(dstruct), C.byref(fo), *forced, _ptr(w_runoff),
+                   _ptr(w_perc), *window, grad.data_ptr(), _ptr(ser), st.data_ptr(), counters=tickets)
         return grad, ser, st
 
     def tangent(self, direction, precip, pet, w_runoff=None, w_perc=None, want_series=False, forcing_group=1, share=0,
-                forcing_map=None):
+                forcing_map=None, d_precip=None, d_pet=None):
         """Forward-mode tangent from a FRESH state (set_internal_states) over the whole forcing series.
 
         direction: {"alpha" | "n" | "ksat": [L, N] tensor} -- the parameter perturbation (missing = 0).
@@ -490,12 +512,19 @@ class LgarEngine:
         Geff trapezoid (LgarDims.tangent_share).
         Returns (grad[N], tangent_runoff[T, N] or None, status[N]) with
         grad[c] = sum_t w_runoff[t, c] * d runoff_t[c] + w_perc[t, c] * d percolation_t[c].  status != 0 marks columns whose
-        tangent integration faulted (their grad entry is not a gradient): callers must check it (autograd.parameter_vjp does)."""
+        tangent integration faulted (their grad entry is not a gradient): callers must check it (autograd.parameter_vjp does).
+        d_precip / d_pet: the direction's part in the FORCING, [T, Nf, forcing_group] each (or None = 0; [T, Nf] when
+        forcing_group is 1): column c runs on (precip, d_precip[t, cf, c % forcing_group]), cf its forcing column, so every
+        lane of a direction group has its own forcing tangent and those that carry a parameter direction hold zeros
+        (lgar_forward_tangent_forced).  The derivative is then along `direction` and the forcing direction together."""
+        if d_precip is not None or d_pet is not None:
+            return self.tangent_window(direction, precip, pet, w_runoff, w_perc, None, False, want_series, forcing_group, share,
+                                       forcing_map, d_precip, d_pet)[:3]
         inputs = self._tangent_inputs(direction, precip, pet, w_runoff, w_perc, forcing_group, share, forcing_map)
         return self._tangent_call("forward_tangent", inputs, forcing_map, want_series)
 
     def tangent_window(self, direction, precip, pet, w_runoff=None, w_perc=None, start=None, keep_state=True, want_series=False,
-                       forcing_group=1, share=0, forcing_map=None):
+                       forcing_group=1, share=0, forcing_map=None, d_precip=None, d_pet=None):
         """tangent() over a WINDOW of rows that may start from a carried state (lgar_forward_tangent_window, include/lgar.h).
 
         start: None = a fresh state: tangent() itself, bit for bit.  An EngineState (snapshot() of a spun-up engine) = a
@@ -507,7 +536,8 @@ class LgarEngine:
         Returns (grad[N], tangent_runoff[T, N] or None, status[N], end): `end` is a TangentState or None.  Columns whose start
         state had faulted keep those fault bits in status.  This engine's own state is neither read nor written; an engine
         made with with_state=False will do.  The other arguments are tangent()'s; with share = W the W columns of a group
-        must hold the same start values as well."""
+        must hold the same start values as well.  d_precip / d_pet are this window's rows of the forcing's tangents; when either
+        is given the call is lgar_forward_tangent_forced, and a TangentState carries across such windows as across any."""
         inputs = self._tangent_inputs(direction, precip, pet, w_runoff, w_perc, forcing_group, share, forcing_map)
         N = self.N
         value = start.value if isinstance(start, TangentState) else start
@@ -534,7 +564,8 @@ class LgarEngine:
                    None if end is None else end.value._struct(), None if end is None else end._struct()]
         win = _capi.LgarTangentWindow(*[None if s is None else C.addressof(s) for s in structs], None if carried is None else carried.grad.data_ptr())
         grad, ser, st = self._tangent_call("forward_tangent_window", inputs, forcing_map, want_series, (C.byref(win),),
-                                           *(() if end is None else (end.grad, end.value.status)))
+                                           *(() if end is None else (end.grad, end.value.status)),
+                                           d_forcing=None if d_precip is None and d_pet is None else (d_precip, d_pet))
         if value is not None:
             st |= value.status & _capi.ST_FAULT_MASK  # (the kernels write the status, they do not read it)
         return grad, ser, st, end

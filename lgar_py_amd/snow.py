@@ -13,9 +13,12 @@ for device="cpu" (its host logic needs no GPU), every call needs the library and
                                           \\-> ice + liq [T, B] -> catchment_moments(SWE observations) -> loss
 
 PET under snow is the caller's concern: the store does not touch it (for example pet * ((ice + liq) == 0) switches it off under
-a pack).  A forcing gradient THROUGH the columns does not exist yet: catchment_snow hands gradients on from its own outputs
-(water, ice, liq) to its inputs, and the columns give none with respect to their forcing, so a loss on runoff does not reach the
-snow parameters -- a loss on the pack series does.
+a pack).  A reverse-mode forcing gradient THROUGH the columns does not exist yet: catchment_snow hands gradients on from its own
+outputs (water, ice, liq) to its inputs, and the columns give none with respect to their forcing, so through catchment_snow a loss
+on runoff does not reach the snow parameters -- a loss on the pack series does.  The forward-mode way does: CatchmentSnow.tangent
+(lgar_catchment_snow_tangent) gives d water along the parameters, catchment_snow_directions packs it as the
+forcing.ForcingDirections that autograd.lgar_series(forcing_directions=) integrates beside the soil directions (DESIGN.md
+section 20).
 """
 import numpy as np
 import torch
@@ -94,6 +97,44 @@ class CatchmentSnow:
             self._open(self.device), self.device, p, ta, self.par, self.dt_h, state_in, want_state, bool(pack)))
         return (w, ice, liq) if pack else w
 
+    def tangent(self, precip, temp, n_dirs, dp=None, dta=None, dpar=None, state=None, dstate=None, out=None, k0=0, pack=False,
+                want_state=False):
+        """The forward-mode tangent of run() along n_dirs = D directions at once (lgar_catchment_snow_tangent): the raw call.
+        precip, temp [T, B] and state ([2, B] or None = no pack) are run()'s (nothing is carried here).  Input tangents, None =
+        zeros: dp, dta [D, T, B]; dpar [D, 7, B] (the rows of .par); dstate [D, 2, B].  out: None = a new zero [T, B, k0 + D] block,
+        or a contiguous fp64 [T, B, ld] tensor with ld >= k0 + D: direction k is written to out[:, :, k0 + k] and nothing else is
+        touched -- the [T, B, G] block LgarEngine.tangent takes as d_precip.  Returns (out, dice, dliq, dstate_out): the pack's
+        tangents [D, T, B] with pack=True and the end state's [D, 2, B] with want_state=True, else None."""
+        p = _stage.matrix(precip, "precip", self.B, self.device)
+        T, B, D = int(p.shape[0]), self.B, int(n_dirs)
+        ta = _stage.matrix(temp, "temp", B, self.device, T)
+        state = None if state is None else _state(state, "state", B, self.device)
+
+        def block(x, what, shape):
+            if x is None:
+                return None
+            if (not isinstance(x, torch.Tensor) or tuple(x.shape) != shape or x.dtype != torch.float64 or x.device != p.device
+                    or not x.is_contiguous()):
+                raise LgarError("%s must be a contiguous fp64 %s tensor on %s" % (what, list(shape), self.device))
+            return x
+        dp, dta = block(dp, "dp", (D, T, B)), block(dta, "dta", (D, T, B))
+        dpar, dstate = block(dpar, "dpar", (D, NPAR, B)), block(dstate, "dstate", (D, 2, B))
+        k0 = int(k0)
+        if D < 0 or k0 < 0:
+            raise LgarError("n_dirs and k0 must be >= 0")
+        if out is None:
+            out = torch.zeros(T, B, k0 + D, dtype=torch.float64, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.dim() != 3 or tuple(out.shape[:2]) != (T, B) or out.shape[2] < k0 + D
+              or out.dtype != torch.float64 or out.device != p.device or not out.is_contiguous()):
+            raise LgarError("out must be a contiguous fp64 [%d, %d, ld] tensor on %s with ld >= k0 + D = %d" % (T, B, self.device, k0 + D))
+        z = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=self.device)
+        dice, dliq = (z(D, T, B), z(D, T, B)) if pack else (None, None)
+        dstate_out = z(D, 2, B) if want_state else None
+        _capi.launch(self._open(self.device), "catchment_snow_tangent", self.device, p.data_ptr(), ta.data_ptr(), T, B, self.par.data_ptr(),
+                     self.dt_h, ptr(state), D, ptr(dp), ptr(dta), ptr(dpar), ptr(dstate), out.data_ptr(), int(out.shape[2]), k0, ptr(dice),
+                     ptr(dliq), ptr(dstate_out))
+        return out, dice, dliq, dstate_out
+
     def reset(self):
         """Forget every carried state."""
         self._states = {}
@@ -161,8 +202,35 @@ def catchment_snow(precip, temp, tlo, thi, tm, sfcf, cfmax, cfr, cwh, dt_h, stat
     Parameter values are not validated here (CatchmentSnow validates once; an optimiser keeps tlo <= thi and the four
     non-negative ones by its own transform): the kernels give the IEEE result for whatever they are handed.
 
-    PET under snow is the caller's concern, for example pet * ((ice + liq) == 0).  A forcing gradient through the columns does
-    not exist yet: the gradient of `water` is consumed here, but LgarEngine / lgar_series give none with respect to their
-    forcing, so calibrate the snow parameters on the pack series (CatchmentScore of ice + liq against snow-water-equivalent
-    records).  A lapse rate or elevation bands are a shift of `temp` per cell in torch: temp receives its gradient."""
+    PET under snow is the caller's concern, for example pet * ((ice + liq) == 0).  A reverse-mode forcing gradient through the
+    columns does not exist yet: the gradient of `water` is consumed here, but LgarEngine / lgar_series give none with respect to
+    their forcing, so through this function the snow parameters are calibrated on the pack series (CatchmentScore of ice + liq
+    against snow-water-equivalent records); to calibrate them on runoff or discharge use catchment_snow_directions with
+    lgar_series(forcing_directions=).  A lapse rate or elevation bands are a shift of `temp` per cell in torch: temp receives its gradient."""
     return CatchmentSnow.function(precip, temp, tlo, thi, tm, sfcf, cfmax, cfr, cwh, dt_h, state, return_pack)
+
+
+def catchment_snow_directions(precip, temp, tlo, thi, tm, sfcf, cfmax, cfr, cwh, dt_h, state=None, owner=CatchmentSnow):
+    """(water, fd): the water input [T, B] of the snowpack (a plain tensor) and the forcing.ForcingDirections that carry a loss on
+    the columns' output back to the snow parameters: autograd.lgar_series(..., water, pet, forcing_directions=fd).  precip, temp:
+    fp64 [T, B]; the seven parameters: fp64 [B] tensors or scalars; there is one direction per parameter that requires grad (in
+    the order tlo .. cwh), fd.params are those tensors and fd.d_precip[k] = d water / d params[k], from ONE tangent launch
+    (lgar_catchment_snow_tangent).  state: the initial pack [2, B], a constant.  The parameters are validated as CatchmentSnow
+    validates them.  PET is not touched: fd has no d_pet."""
+    from .forcing import ForcingDirections
+    pars = (tlo, thi, tm, sfcf, cfmax, cfr, cwh)
+    if not isinstance(precip, torch.Tensor) or precip.dim() != 2:
+        raise LgarError("precip must be a fp64 [T, B] tensor")
+    B, device = int(precip.shape[1]), precip.device
+    pars = tuple(torch.as_tensor(v) for v in pars)
+    snow = owner(*[v.detach().to("cpu", torch.float64).expand(B).contiguous() for v in pars], dt_h, device=device)
+    water = snow.run(precip.detach(), temp.detach(), carry=False, state=state)
+    wanted = [j for j, v in enumerate(pars) if v.requires_grad]
+    D, T = len(wanted), int(precip.shape[0])
+    if D == 0:
+        return water, ForcingDirections((), None, None)
+    dpar = torch.zeros(D, NPAR, B, dtype=torch.float64, device=device)
+    for k, j in enumerate(wanted):
+        dpar[k, j] = 1.0
+    dw = snow.tangent(precip.detach(), temp.detach(), D, dpar=dpar, state=state)[0]  # [T, B, D]
+    return water, ForcingDirections(tuple(pars[j] for j in wanted), d_precip=dw.permute(2, 0, 1).contiguous())
