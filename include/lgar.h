@@ -791,6 +791,88 @@ int32_t lgar_catchment_snow_tangent(const double *p, const double *ta, int32_t n
                                     const double *dstate_in, double *dw, int32_t ld, int32_t k0, double *dice, double *dliq,
                                     double *dstate_out, void *stream);
 
+/* Catchment canopy: an interception store per forcing cell AHEAD of the snowpack and the columns.  All
+ * arrays fp64, cell fastest: the precipitation rate p[T][B] and the PET rate e[T][B] (the engine's forcing unit), the relative leaf
+ * area lai[T][B] (NULL: 1, and then cap = cmax is formed once with no multiplication), par[3][B] = cmax (the depth the canopy
+ * holds per unit lai), fe (the wet-canopy evaporation factor), cover (the vegetated fraction), state_in[1][B] = s, the depth held
+ * (NULL: +0.0).  T = n_rows, B = n_cells.  Outputs: the throughfall rate w[T][B], the PET left to the columns pet_out[T][B], and
+ * optionally (both or neither) store[T][B], the depth held behind each row, and evap[T][B], the wet-canopy evaporation rate.  One
+ * cell b, with fc = fe * cover (once), for t = 0 .. T - 1:
+ *     pd   = p[t][b] * dt_h;      ed = e[t][b] * dt_h
+ *     hit  = cover * pd;          direct = pd - hit
+ *     cap  = cmax * lai[t][b]
+ *     s1   = s + hit;             full = s1 > cap
+ *     drip = full ? s1 - cap : 0.0
+ *     s2   = full ? cap : s1
+ *     dem  = fc * ed;             lim = dem > s2
+ *     ei   = lim ? s2 : dem
+ *     s    = s2 - ei
+ *     neg  = ei > ed
+ *     r    = neg ? 0.0 : ed - ei
+ *     w[t][b] = (direct + drip) / dt_h;   pet_out[t][b] = r / dt_h;   store[t][b] = s;   evap[t][b] = ei / dt_h
+ * in exactly this association, without contraction (-ffp-contract=off), IEEE divisions, no libm.  state_out = s after the last
+ * row (NULL: not wanted).  Every output is WRITTEN, not added to.  Every decision is a select, and ties go where the selects send
+ * them: s1 == cap holds (no drip), dem == s2 is demand-limited (ei = dem), ei == ed leaves r = ed - ei = +0.0.
+ *   Water balance, in real arithmetic: dt_h sum p = dt_h sum w + dt_h sum evap + s_T - s_0.
+ *   Empty store: T = 0 copies the state (zeros when state_in is NULL); B = 0 is a no-op.
+ *   Independence: the result for b is a pure function of column b of p, e, lai and par and of state_in[0][b].  A NaN fails every
+ *     comparison and takes the last alternative.  A NaN in p[t][b]: w of row t is NaN, evap and pet_out of row t are clean (ei =
+ *     dem), store is NaN from row t on; in the later rows drip = 0.0 and ei = dem, so w = direct / dt_h, evap and pet_out are clean
+ *     -- the store carries the NaN.  A NaN in e[t][b]: evap and pet_out of row t are NaN, w of row t is clean, store is NaN from
+ *     row t on.  A NaN in lai[t][b]: full is false, the row holds all that hit it, and the NaN is gone.  No other cell sees any.
+ *   Bare ground: with cover = 0, a zero state and dt_h a power of two, w has p's bits and pet_out has e's bits.
+ * Refused with LGAR_E_ARG: negative sizes, a dt_h that is not finite or <= 0, exactly one of store / evap given, a null pointer
+ * the sizes say will be read or written (T > 0: p, e, par, w, pet_out).  Parameter VALUES are not policed.  One launch on
+ * `stream`; offsets are 64-bit. */
+int32_t lgar_catchment_canopy(const double *p, const double *e, const double *lai, int32_t n_rows, int32_t n_cells, const double *par,
+                              double dt_h, const double *state_in, double *state_out, double *w, double *pet_out, double *store,
+                              double *evap, void *stream);
+
+/* The adjoint of the canopy: from gw[T][B], gpet[T][B] and gstore[T][B], gevap[T][B] (each NULL: zeros), the incoming gradients of
+ * w, pet_out, store and evap, the gradients with respect to p (gp[T][B]), to e (ge[T][B]), to lai (glai[T][B]; NULL: not wanted),
+ * to the parameters (gpar[3][B] in par's order; NULL: not wanted) and to the initial state (gstate[1][B]; NULL: not wanted).
+ * store is the series the forward stored for the same p, e, lai, par, dt_h, state_in.  Row t is re-formed from store[t - 1][b]
+ * (row 0: state_in, or +0.0) through the forward's own row function: every flag below has the forward's bits.  With ls = +0.0
+ * and the accumulators gcmax, gfc, gcover from +0.0, lai = lai[t][b] (NULL: 1.0), for t = T - 1 .. 0:
+ *     ls   = ls + gstore[t][b];  gtf = gw[t][b] / dt_h;  gr = gpet[t][b] / dt_h;  gei = gevap[t][b] / dt_h
+ *     dr   = neg ? 0.0 : gr;          dei  = (gei - dr) - ls
+ *     ds2  = lim ? ls + dei : ls;     ddem = lim ? 0.0 : dei
+ *     gfc  = lim ? gfc : gfc + ddem * ed;          ged = dr + ddem * fc
+ *     ds1  = full ? gtf : ds2;        dcap = full ? ds2 - gtf : 0.0
+ *     gcmax = full ? gcmax + dcap * lai : gcmax;   glai[t][b] = dcap * cmax
+ *     dhit = ds1 - gtf;               gcover = gcover + dhit * pd
+ *     gp[t][b] = (gtf + dhit * cover) * dt_h;      ge[t][b] = ged * dt_h;      ls = ds1
+ * and after row 0: gfe = gfc * cover, gcover = gcover + gfc * fe, gstate = ls.  The regimes are selects on the forward's own
+ * flags, so a tie belongs where the forward sent it; an accumulator that receives no term in a row keeps its bits (a select of the
+ * accumulator, not an added zero).  Every output element is WRITTEN; T = 0 writes zeros.  Refused with LGAR_E_ARG: negative sizes,
+ * a dt_h that is not finite or <= 0, and (T, B > 0) a null gw, gpet, p, e, store, par, gp or ge. */
+int32_t lgar_catchment_canopy_grad(const double *gw, const double *gpet, const double *gstore, const double *gevap, const double *p,
+                                   const double *e, const double *lai, const double *store, int32_t n_rows, int32_t n_cells,
+                                   const double *par, double dt_h, const double *state_in, double *gp, double *ge, double *glai,
+                                   double *gpar, double *gstate, void *stream);
+
+/* Forward-mode tangent of lgar_catchment_canopy along n_dirs = D directions at once: one lane per (cell, direction), lane
+ * k * B + b, everything fp64.  p, e, lai, par, dt_h, state_in are the forward's; the value recurrence is the forward's own, so
+ * every decision has its bits.  Input tangents, NULL = zeros: dp, de, dlai [D][T][B]; dpar [D][3][B]; dstate_in [D][B].  Once per
+ * lane fc' = fe' * cover + fe * cover', and per row, with s' from dstate_in, lai = lai[t][b] (NULL: 1.0), lai' = dlai[k][t][b]:
+ *     pd'   = dp[k][t][b] * dt_h;           ed' = de[k][t][b] * dt_h
+ *     hit'  = cover' * pd + cover * pd';    direct' = pd' - hit'
+ *     cap'  = cmax' * lai + cmax * lai'
+ *     s1'   = s' + hit';   drip' = full ? s1' - cap' : 0.0;   s2' = full ? cap' : s1'
+ *     dem'  = fc' * ed + fc * ed';          ei' = lim ? s2' : dem'
+ *     s'    = s2' - ei';   r' = neg ? 0.0 : ed' - ei'
+ * Outputs: dw(t, b, k) = (direct' + drip') / dt_h at dw[(t * B + b) * ld + k0 + k] and dpet(t, b, k) = r' / dt_h at the same
+ * offset of dpet (NULL: not wanted), with ld >= k0 + D, so the call writes straight into the two [n_steps][Nf][G] blocks of forcing
+ * tangents lgar_forward_tangent_forced reads (G = ld); the other elements of a row of ld are not touched.  Optional dstore
+ * (s') and devap (ei' / dt_h) [D][T][B] (both or neither) and dstate_out [D][B].  T = 0 copies dstate.  Refused with LGAR_E_ARG:
+ * negative sizes or k0, ld < k0 + D, a dt_h that is not finite or <= 0, exactly one of dstore / devap, and (T, B, D > 0) a null
+ * p, e, par or dw. */
+int32_t lgar_catchment_canopy_tangent(const double *p, const double *e, const double *lai, int32_t n_rows, int32_t n_cells,
+                                      const double *par, double dt_h, const double *state_in, int32_t n_dirs, const double *dp,
+                                      const double *de, const double *dlai, const double *dpar, const double *dstate_in, double *dw,
+                                      double *dpet, int32_t ld, int32_t k0, double *dstore, double *devap, double *dstate_out,
+                                      void *stream);
+
 /* Run totals of a run cut into several lgar_forward calls.  lgar_forward sums a call's accumulators step by step from zero
  * and adds that sum to LgarState.totals, so a chunked run adds several partial sums where one call adds one: the same numbers in
  * another order, equal to the last bits only.  This replays the one-call order over series the chunks stored: for every j < 7

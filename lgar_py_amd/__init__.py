@@ -11,7 +11,8 @@ from .network import (CatchmentNetwork, NetworkPools, manning_reach_parameters, 
                       network_route_pool, weir_pool_parameters)
 from .scores import CatchmentScore, catchment_moments  # noqa: F401
 from .snow import CatchmentSnow, catchment_snow, catchment_snow_directions  # noqa: F401
+from .canopy import CatchmentCanopy, catchment_canopy, catchment_canopy_directions  # noqa: F401
 
 __all__ = ["LgarEngine", "EngineState", "TangentState", "LgarError", "LgarStatusError", "leaf_batch", "leaf_tangent_batch", "CatchmentMap", "catchment_sum", "CatchmentRouting", "catchment_route", "CatchmentScore", "catchment_moments", "CatchmentNetwork", "network_route", "network_route_mc", "manning_reach_parameters", "NetworkPools", "network_route_pool", "weir_pool_parameters",
-           "muskingum_coefficients", "CatchmentBaseflow", "catchment_baseflow", "CatchmentSnow", "catchment_snow", "catchment_snow_directions", "ForcingMap", "ForcingDirections", "scaled_forcing", "ACC_NAMES", "FMAX",
+           "muskingum_coefficients", "CatchmentBaseflow", "catchment_baseflow", "CatchmentSnow", "catchment_snow", "catchment_snow_directions", "CatchmentCanopy", "catchment_canopy", "catchment_canopy_directions", "ForcingMap", "ForcingDirections", "scaled_forcing", "ACC_NAMES", "FMAX",
            "LMAX"]

@@ -32,7 +32,7 @@ STATUS_NAMES = {1: "NaN", 2: "negative pow base", 4: "theta order", 8: "front ov
 ABI_VERSION = 4  # LGAR_ABI_VERSION of include/lgar.h this binding mirrors
 EXPORTS = ["lgar_version", "lgar_abi_version", "lgar_sizeof_dims", "lgar_fmax", "lgar_lmax", "lgar_cooperating_lanes", "lgar_state_init", "lgar_forward", "lgar_forward_tangent", "lgar_forward_tangent_window", "lgar_forward_tangent_forced",
            "lgar_soil_moisture", "lgar_totals_replay", "lgar_catchment_sums", "lgar_catchment_spread", "lgar_catchment_route", "lgar_catchment_route_grad",
-           "lgar_catchment_moments_workspace", "lgar_catchment_moments", "lgar_catchment_moments_grad", "lgar_network_route", "lgar_network_route_grad", "lgar_network_route_mc", "lgar_network_route_mc_grad", "lgar_network_route_pool", "lgar_network_route_pool_grad", "lgar_catchment_baseflow", "lgar_catchment_baseflow_grad", "lgar_catchment_snow", "lgar_catchment_snow_grad", "lgar_catchment_snow_tangent", "lgar_leaf_batch", "lgar_leaf_tangent_batch", "lgar_valu_probe", "lgar_valu_probe_insts"]
+           "lgar_catchment_moments_workspace", "lgar_catchment_moments", "lgar_catchment_moments_grad", "lgar_network_route", "lgar_network_route_grad", "lgar_network_route_mc", "lgar_network_route_mc_grad", "lgar_network_route_pool", "lgar_network_route_pool_grad", "lgar_catchment_baseflow", "lgar_catchment_baseflow_grad", "lgar_catchment_snow", "lgar_catchment_snow_grad", "lgar_catchment_snow_tangent", "lgar_catchment_canopy", "lgar_catchment_canopy_grad", "lgar_catchment_canopy_tangent", "lgar_leaf_batch", "lgar_leaf_tangent_batch", "lgar_valu_probe", "lgar_valu_probe_insts"]
 
 
 class LgarDims(C.Structure):
@@ -196,6 +196,13 @@ def load():
     if hasattr(lib, "lgar_catchment_snow_tangent") or not os.environ.get("LGAR_LIB"):  # (a library selected by hand may predate it)
         lib.lgar_catchment_snow_tangent.restype = i32
         lib.lgar_catchment_snow_tangent.argtypes = [vp, vp, i32, i32, vp, dbl, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    if hasattr(lib, "lgar_catchment_canopy") or not os.environ.get("LGAR_LIB"):  # (a library selected by hand may predate it)
+        lib.lgar_catchment_canopy.restype = i32
+        lib.lgar_catchment_canopy.argtypes = [vp, vp, vp, i32, i32, vp, dbl, vp, vp, vp, vp, vp, vp, vp]
+        lib.lgar_catchment_canopy_grad.restype = i32
+        lib.lgar_catchment_canopy_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, dbl, vp, vp, vp, vp, vp, vp, vp]
+        lib.lgar_catchment_canopy_tangent.restype = i32
+        lib.lgar_catchment_canopy_tangent.argtypes = [vp, vp, vp, i32, i32, vp, dbl, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
     lib.lgar_leaf_batch.restype = i32
     lib.lgar_leaf_batch.argtypes = [i32, i32, vp, vp, dbl, vp, vp, vp, vp, vp, i32, dbl, vp, i32, vp]
     if hasattr(lib, "lgar_leaf_tangent_batch") or not os.environ.get("LGAR_LIB"):  # (a library selected by hand may predate it)

@@ -210,13 +210,19 @@ def catchment_snow(precip, temp, tlo, thi, tm, sfcf, cfmax, cfr, cwh, dt_h, stat
     return CatchmentSnow.function(precip, temp, tlo, thi, tm, sfcf, cfmax, cfr, cwh, dt_h, state, return_pack)
 
 
-def catchment_snow_directions(precip, temp, tlo, thi, tm, sfcf, cfmax, cfr, cwh, dt_h, state=None, owner=CatchmentSnow):
+def catchment_snow_directions(precip, temp, tlo, thi, tm, sfcf, cfmax, cfr, cwh, dt_h, state=None, owner=CatchmentSnow, upstream=None):
     """(water, fd): the water input [T, B] of the snowpack (a plain tensor) and the forcing.ForcingDirections that carry a loss on
     the columns' output back to the snow parameters: autograd.lgar_series(..., water, pet, forcing_directions=fd).  precip, temp:
     fp64 [T, B]; the seven parameters: fp64 [B] tensors or scalars; there is one direction per parameter that requires grad (in
     the order tlo .. cwh), fd.params are those tensors and fd.d_precip[k] = d water / d params[k], from ONE tangent launch
     (lgar_catchment_snow_tangent).  state: the initial pack [2, B], a constant.  The parameters are validated as CatchmentSnow
-    validates them.  PET is not touched: fd has no d_pet."""
+    validates them.  PET is not touched: fd has no d_pet.
+
+    upstream: None, or the ForcingDirections u of a stage AHEAD of the snowpack (canopy.catchment_canopy_directions), whose
+    d_precip is the tangent of this call's `precip`.  Then ONE snow-tangent launch runs over u.K + D directions: the upstream
+    rows enter through dp with a zero dpar, the snow rows are as before; fd.params = u.params + the snow's, fd.d_precip runs along
+    all of them, and fd.d_pet = u.d_pet padded with zero rows for the snow parameters (None if u has none): the snowpack does not
+    touch PET."""
     from .forcing import ForcingDirections
     pars = (tlo, thi, tm, sfcf, cfmax, cfr, cwh)
     if not isinstance(precip, torch.Tensor) or precip.dim() != 2:
@@ -227,6 +233,8 @@ def catchment_snow_directions(precip, temp, tlo, thi, tm, sfcf, cfmax, cfr, cwh,
     water = snow.run(precip.detach(), temp.detach(), carry=False, state=state)
     wanted = [j for j, v in enumerate(pars) if v.requires_grad]
     D, T = len(wanted), int(precip.shape[0])
+    if upstream is not None and upstream.K:
+        return water, _composed(snow, upstream, precip.detach(), temp.detach(), state, tuple(pars[j] for j in wanted), wanted)
     if D == 0:
         return water, ForcingDirections((), None, None)
     dpar = torch.zeros(D, NPAR, B, dtype=torch.float64, device=device)
@@ -234,3 +242,24 @@ def catchment_snow_directions(precip, temp, tlo, thi, tm, sfcf, cfmax, cfr, cwh,
         dpar[k, j] = 1.0
     dw = snow.tangent(precip.detach(), temp.detach(), D, dpar=dpar, state=state)[0]  # [T, B, D]
     return water, ForcingDirections(tuple(pars[j] for j in wanted), d_precip=dw.permute(2, 0, 1).contiguous())
+
+
+def _composed(snow, u, precip, temp, state, params, wanted):
+    """The directions of catchment_snow_directions behind an upstream stage u: u.K rows that enter through dp, then one row per
+    wanted snow parameter through dpar, in one tangent launch."""
+    from .forcing import ForcingDirections
+    T, B, D = int(precip.shape[0]), int(precip.shape[1]), len(wanted)
+    K = u.K + D
+    if u.d_precip is None or tuple(u.d_precip.shape) != (u.K, T, B):
+        raise LgarError("upstream.d_precip must be the [%d, %d, %d] tangent of precip" % (u.K, T, B))
+    dp = torch.zeros(K, T, B, dtype=torch.float64, device=precip.device)
+    dp[:u.K] = u.d_precip.to(precip.device, torch.float64)
+    dpar = torch.zeros(K, NPAR, B, dtype=torch.float64, device=precip.device)
+    for k, j in enumerate(wanted):
+        dpar[u.K + k, j] = 1.0
+    dw = snow.tangent(precip, temp, K, dp=dp, dpar=dpar, state=state)[0]  # [T, B, K]
+    d_pet = None
+    if u.d_pet is not None:
+        d_pet = torch.zeros(K, T, B, dtype=torch.float64, device=precip.device)
+        d_pet[:u.K] = u.d_pet.to(precip.device, torch.float64)
+    return ForcingDirections(tuple(u.params) + tuple(params), d_precip=dw.permute(2, 0, 1).contiguous(), d_pet=d_pet)
