@@ -310,6 +310,36 @@ int32_t lgar_soil_moisture(const LgarDims *dims, const LgarParams *params, const
                            int32_t n_bins, int32_t what, void *out, const void *weights, double *basin, int32_t dtype,
                            void *stream);
 
+/* The tangent of the soil-moisture output: the derivative of lgar_soil_moisture's bins along the direction a tangent state was
+ * integrated for (state_out / dstate_out of lgar_forward_tangent_window, passed as they are: `state` is the value state, `dstate`
+ * its tangent parts; dims->n_columns = M is the number of lanes of that state).  With lgar_soil_moisture's notation and the
+ * tangents d'_j, theta'_j, t'_j = d'_{j-1} (same layer tag) or +0.0 (a layer's top: thickness is not differentiated), bin
+ * i = [a, b] has
+ *     in(x) = x >= a && x < b
+ *     S'_i  = sum_j  theta'_j * (clip(d_j, a, b) - clip(t_j, a, b))  +  (in(d_j) ? theta_j * d'_j : 0.0)  -  (in(t_j) ? theta_j * t'_j : 0.0)
+ * in front order, per front acc = ((acc + first) + second) - third; fp64 whatever `dtype`; every decision is a select.
+ * The tie rule: clip's two one-sided derivatives differ where a depth sits exactly on an edge.  `in` is half-open, so such a depth
+ * lies in exactly one of two adjacent bins (the lower one, whose a it equals), and the bins that cover a column sum to the tangent
+ * of the stored volume, sum_j theta'_j (d_j - t_j) + theta_j (d'_j - t'_j), also with a front on an edge; counting it in both
+ * bins or in neither would break that closure.
+ * what: 1 = storage: m'_i = S'_i.  0 = m'_i = w_i > 0 ? S'_i / w_i : +0.0, w_i being lgar_soil_moisture's in-column width, a
+ *   constant: below the column the value is NaN, its tangent is zero.
+ * Outputs, either or both:
+ *   out: [n_bins][M] (dtype), m'_i rounded once; or NULL.
+ *   cot, grad (both or neither): the contraction into the gradient a run of tangent windows carries.  cot: fp64 [n_bins][M / group];
+ *     lane c reads column c / group (the forcing_group convention of the tangent launches).  acc = +0.0; for i ascending:
+ *     acc = acc + (live_i ? cot_i * m'_i : 0.0) with the unrounded fp64 m'_i, live_i = w_i > 0 for what = 0 and true for what = 1 (a
+ *     select: a NaN cotangent under a dead bin is discarded); then grad[c] = (dtype)((double)grad[c] + acc), in place: grad is
+ *     [M] (dtype).
+ * edges, n_bins: as in lgar_soil_moisture (NULL: each lane's own layers).  n_fronts is clamped to the state's front_slots and layer
+ * tags to n_layers - 1 exactly as there; only state->depth, theta, flags, n_fronts, dstate->depth, theta and params->thickness
+ * are read; nothing of either state is written.
+ * LGAR_E_ARG: what lgar_soil_moisture refuses (but M = 0, which returns 0 without a launch); a null dstate, dstate->depth or
+ * dstate->theta; neither out nor (cot and grad); exactly one of cot / grad; group < 1 or M not a multiple of group. */
+int32_t lgar_soil_moisture_tangent(const LgarDims *dims, const LgarParams *params, const LgarState *state, const LgarState *dstate,
+                                   const double *edges, int32_t n_bins, int32_t what, void *out, const double *cot, int32_t group,
+                                   void *grad, int32_t dtype, void *stream);
+
 /* Catchment sums: per-row sums of a stored series over MANY catchments, out[t][b] for B catchments at once (LgarStepOut.basin
  * is the one-catchment case; what a NextGen-style job compares with observations is the [T][B] matrix of catchment runoff).
  *

@@ -31,7 +31,7 @@ STATUS_NAMES = {1: "NaN", 2: "negative pow base", 4: "theta order", 8: "front ov
                 32: "front reached domain bottom", 64: "structural error"}
 ABI_VERSION = 4  # LGAR_ABI_VERSION of include/lgar.h this binding mirrors
 EXPORTS = ["lgar_version", "lgar_abi_version", "lgar_sizeof_dims", "lgar_fmax", "lgar_lmax", "lgar_cooperating_lanes", "lgar_state_init", "lgar_forward", "lgar_forward_tangent", "lgar_forward_tangent_window", "lgar_forward_tangent_forced",
-           "lgar_soil_moisture", "lgar_totals_replay", "lgar_catchment_sums", "lgar_catchment_spread", "lgar_catchment_route", "lgar_catchment_route_grad",
+           "lgar_soil_moisture", "lgar_soil_moisture_tangent", "lgar_totals_replay", "lgar_catchment_sums", "lgar_catchment_spread", "lgar_catchment_route", "lgar_catchment_route_grad",
            "lgar_catchment_moments_workspace", "lgar_catchment_moments", "lgar_catchment_moments_grad", "lgar_network_route", "lgar_network_route_grad", "lgar_network_route_mc", "lgar_network_route_mc_grad", "lgar_network_route_pool", "lgar_network_route_pool_grad", "lgar_catchment_baseflow", "lgar_catchment_baseflow_grad", "lgar_catchment_snow", "lgar_catchment_snow_grad", "lgar_catchment_snow_tangent", "lgar_catchment_canopy", "lgar_catchment_canopy_grad", "lgar_catchment_canopy_tangent", "lgar_leaf_batch", "lgar_leaf_tangent_batch", "lgar_valu_probe", "lgar_valu_probe_insts"]
 
 
@@ -150,6 +150,10 @@ def load():
         lib.lgar_soil_moisture.argtypes = [p(LgarDims), p(LgarParams), p(LgarState), vp, i32, i32, vp, vp, vp, i32, vp]
         lib.lgar_totals_replay.restype = i32
         lib.lgar_totals_replay.argtypes = [p(LgarDims), p(LgarStepOut), i32, vp, i32, vp]
+    if hasattr(lib, "lgar_soil_moisture_tangent") or not os.environ.get("LGAR_LIB"):  # (a library selected by hand may predate it)
+        lib.lgar_soil_moisture_tangent.restype = i32
+        lib.lgar_soil_moisture_tangent.argtypes = [p(LgarDims), p(LgarParams), p(LgarState), p(LgarState), vp, i32, i32, vp, vp, i32,
+                                                   vp, i32, vp]
     if hasattr(lib, "lgar_catchment_sums") or not os.environ.get("LGAR_LIB"):  # (a library selected by hand may predate them)
         lib.lgar_catchment_sums.restype = i32
         lib.lgar_catchment_sums.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp]

@@ -42,7 +42,31 @@ def _forcing_lanes(fd, part, T, Nf, dtype, device):
     return out
 
 
-def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcing_map=None, start=None, forcing_directions=None):
+def _windowed_tangent(e, direction, precip, pet, w_runoff, w_perc, start, moisture, group, kw, fkw):
+    """One group of directions over the whole run in windows of `every` rows, the state carried (LgarEngine.tangent_window: the
+    bits of one call), with snapshot s's cotangent contracted into the carried gradient after window s
+    (LgarEngine.soil_moisture_tangent); trailing T % every rows form a last window without one.  moisture = (every, device
+    edges or None, number of bins, what, cot [T // every, bins, N] fp64).  Returns (grad[M], status[M])."""
+    every, e_dev, n_bins, what, cot = moisture
+    T = int(precip.shape[0])
+    rows = lambda t, lo, hi: None if t is None else t[lo:hi]
+    grad = torch.zeros(e.N, dtype=e.dtype, device=e.device)
+    status = torch.zeros(e.N, dtype=torch.int32, device=e.device)
+    state = start
+    for lo in range(0, T, every):
+        hi = min(lo + every, T)
+        full = hi - lo == every
+        grad, _, st, end = e.tangent_window(direction, precip[lo:hi], pet[lo:hi], w_runoff=rows(w_runoff, lo, hi), w_perc=rows(w_perc, lo, hi),
+                                            start=state, keep_state=full, **kw, **{nm: d[lo:hi] for nm, d in fkw.items()})
+        status |= st
+        if full:
+            e._moisture_tangent_launch(end, e_dev, n_bins, what, None, cot[lo // every], group)
+            state = end
+    return grad, status
+
+
+def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcing_map=None, start=None, forcing_directions=None,
+                  moisture=None):
     """Vector-Jacobian product for every (kind, layer) in `wanted` (list of (kind, l)).
     Returns ({(kind, l): grad[N]}, tangent_status[N]).  Columns are independent, so the directions are laid side by side as
     len(wanted) * N columns of a single launch (fills the chip even for ensembles of 10^5 columns; very large jobs go in
@@ -57,8 +81,23 @@ def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcin
     forcing_directions: a forcing.ForcingDirections over the run's forcing columns; `wanted` may then hold ("forcing", k) as
     well: lane k of a column integrates the forcing tangent d_precip[k] / d_pet[k] of the column's forcing cell
     (lgar_forward_tangent_forced) and the result is the column's own share of d loss / d params[k] of its cell.  Groups without
-    such a lane are launched as they always were."""
+    such a lane are launched as they always were.
+    moisture: None, or (every, edges, what, cot) with cot [T // every, bins, N] the cotangent of the soil-moisture snapshots
+    LgarEngine.run_with_soil_moisture(every, edges, what) takes: every group of directions then goes through tangent_window in
+    windows of `every` rows, the state carried from `start`, and after window s the contraction of snapshot s's cotangent with the
+    tangent of the bins is added to the carried gradient (LgarEngine.soil_moisture_tangent).  The result is the vector-Jacobian
+    product of the two series AND the snapshots.  None is the code path as it always was."""
     L, N, D = eng.L, eng.N, len(wanted)
+    if moisture is not None:
+        every, edges, what, cot = moisture
+        every = int(every)
+        if every < 1:
+            raise LgarError("every must be >= 1")
+        e_dev, n_bins = eng._moisture_bins(edges, what, need_state=False)
+        want = (int(precip.shape[0]) // every, n_bins, N)
+        if (not isinstance(cot, torch.Tensor) or tuple(cot.shape) != want or cot.dtype != torch.float64 or cot.device != eng.status.device):
+            raise LgarError("the soil-moisture cotangent must be a fp64 %s tensor on %s" % (list(want), eng.device))
+        moisture = (every, e_dev, n_bins, what, cot.contiguous())
     fd = forcing_directions
     T, Nf = (int(precip.shape[0]), int(precip.shape[1])) if fd is not None else (0, 0)
     out = {}
@@ -84,7 +123,10 @@ def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcin
                 dmat = torch.zeros(L, N, dtype=eng.dtype, device=eng.device)
                 dmat[l] = 1.0
                 direction, fkw = {kind: dmat}, {}
-            if start is None:
+            if moisture is not None:
+                out[(kind, l)], st = _windowed_tangent(eng, direction, precip, pet, w_runoff, w_perc, start, moisture, 1,
+                                                       dict(forcing_map=forcing_map), fkw)
+            elif start is None:
                 out[(kind, l)], _, st = eng.tangent(direction, precip, pet, w_runoff=w_runoff, w_perc=w_perc, forcing_map=forcing_map, **fkw)
             else:
                 out[(kind, l)], _, st, _ = eng.tangent_window(direction, precip, pet, w_runoff=w_runoff, w_perc=w_perc,
@@ -102,9 +144,13 @@ def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcin
                 dirs[kind][l, b::Dg] = 1.0
         # forcing / weights broadcast by the kernel (forcing_group); the SAME map, not replicated: entry c // Dg of the launch is
         # the original column, and the incoming [T, N] gradient is the [T, Dg * N // Dg] weight array as it is
-        kw = dict(w_runoff=w_runoff, w_perc=w_perc, forcing_group=Dg, share=Dg if share else 0, forcing_map=forcing_map)
-        kw.update(_forcing_lanes(fd, part, T, Nf, eng.dtype, eng.device))
-        if start is None:
+        layout = dict(forcing_group=Dg, share=Dg if share else 0, forcing_map=forcing_map)
+        fkw = _forcing_lanes(fd, part, T, Nf, eng.dtype, eng.device)
+        kw = dict(w_runoff=w_runoff, w_perc=w_perc, **layout, **fkw)
+        if moisture is not None:
+            g, st = _windowed_tangent(big, dirs, precip, pet, w_runoff, w_perc, None if start is None else start.expand(Dg), moisture,
+                                      Dg, layout, fkw)
+        elif start is None:
             g, _, st = big.tangent(dirs, precip, pet, **kw)
         else:
             g, _, st, _ = big.tangent_window(dirs, precip, pet, start=start.expand(Dg), keep_state=False, **kw)
@@ -123,94 +169,112 @@ def parameter_vjp(eng, precip, pet, w_runoff, w_perc, wanted, check=True, forcin
     return out, status
 
 
+def _open_run(ctx, alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, engine_kw):
+    """What the forward passes of the series nodes do alike before the run: the engine over the detached parameters, the forcing as
+    the backward pass will pair it with the incoming gradient, the given state restored, and on ctx what backward needs.  Returns
+    (engine, precip, pet, forcing_map, check, state_out, status_out)."""
+    engine_kw = dict(engine_kw)
+    fd = engine_kw.pop("forcing_directions", None)
+    check = engine_kw.pop("check", True)
+    status_out = engine_kw.pop("status_out", None)
+    fmap = engine_kw.pop("forcing_map", None)
+    start = engine_kw.pop("initial_state", None)
+    state_out = engine_kw.pop("state_out", None)
+    eng = LgarEngine(alpha.detach(), n.detach(), ksat.detach(), theta_e, theta_r, thickness, **engine_kw)
+    precip, pet = torch.as_tensor(precip), torch.as_tensor(pet)
+    if fd is not None and fmap is None and (precip.dim() != 2 or precip.shape[1] != eng.N):
+        raise LgarError("forcing_directions need [T, N] forcing or a forcing_map, not the broadcast [T, Nf] layout: a forcing "
+                        "cell there is read by columns that are not one group, and its parameters' lanes have no place")
+    if fmap is not None:
+        pass  # [T, B] forcing through the map, forward and backward: nothing is expanded (the weights do not go through it)
+    elif precip.dim() == 2 and precip.shape[1] != eng.N:
+        # broadcast forcing [T, Nf]: the backward pass pairs the forcing with the incoming [T, N] gradient column by
+        # column (the tangent kernels take one layout for both), so the series is expanded here, once
+        if eng.N % max(int(precip.shape[1]), 1) != 0 or precip.shape != pet.shape:
+            raise LgarError("forcing must be [T, N] or [T, Nf] with Nf dividing N = %d; got %s / %s"
+                            % (eng.N, tuple(precip.shape), tuple(pet.shape)))
+        rep = eng.N // int(precip.shape[1])
+        precip, pet = precip.repeat(1, rep).contiguous(), pet.repeat(1, rep).contiguous()  # column c reads c % Nf
+    if fd is not None:
+        if fd.K and fd.shape != (fd.K, int(precip.shape[0]), int(precip.shape[1])):
+            raise LgarError("forcing_directions hold %s, the forcing is [T, B] = %s: d_precip / d_pet must be [K, T, B]"
+                            % (fd.shape, tuple(precip.shape)))
+    if start is not None:
+        eng.restore(start)  # (in place of the fresh state the constructor left)
+    ctx.engine = eng
+    ctx.forcing = (precip, pet)
+    ctx.forcing_map = fmap
+    ctx.start = start
+    ctx.forcing_directions = fd
+    ctx.in_dtypes = (alpha.dtype, n.dtype, ksat.dtype)
+    ctx.check = check
+    ctx.status_out = status_out
+    return eng, precip, pet, fmap, check, state_out, status_out
+
+
 class LgarSeriesFunction(torch.autograd.Function):
     """(alpha, n, ksat)[L, N] -> (runoff, percolation)[T, N] from a fresh state, or from a given one held fixed; differentiable
     in alpha/n/ksat and, through forcing_directions, in the parameters the forcing was computed from (the inputs behind engine_kw)."""
 
     @staticmethod
     def forward(ctx, alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, engine_kw, *forcing_params):
-        engine_kw = dict(engine_kw)
-        fd = engine_kw.pop("forcing_directions", None)
-        check = engine_kw.pop("check", True)
-        status_out = engine_kw.pop("status_out", None)
-        fmap = engine_kw.pop("forcing_map", None)
-        start = engine_kw.pop("initial_state", None)
-        state_out = engine_kw.pop("state_out", None)
-        eng = LgarEngine(alpha.detach(), n.detach(), ksat.detach(), theta_e, theta_r, thickness, **engine_kw)
-        precip, pet = torch.as_tensor(precip), torch.as_tensor(pet)
-        if fd is not None and fmap is None and (precip.dim() != 2 or precip.shape[1] != eng.N):
-            raise LgarError("forcing_directions need [T, N] forcing or a forcing_map, not the broadcast [T, Nf] layout: a forcing "
-                            "cell there is read by columns that are not one group, and its parameters' lanes have no place")
-        if fmap is not None:
-            pass  # [T, B] forcing through the map, forward and backward: nothing is expanded (the weights do not go through it)
-        elif precip.dim() == 2 and precip.shape[1] != eng.N:
-            # broadcast forcing [T, Nf]: the backward pass pairs the forcing with the incoming [T, N] gradient column by
-            # column (the tangent kernels take one layout for both), so the series is expanded here, once
-            if eng.N % max(int(precip.shape[1]), 1) != 0 or precip.shape != pet.shape:
-                raise LgarError("forcing must be [T, N] or [T, Nf] with Nf dividing N = %d; got %s / %s"
-                                % (eng.N, tuple(precip.shape), tuple(pet.shape)))
-            rep = eng.N // int(precip.shape[1])
-            precip, pet = precip.repeat(1, rep).contiguous(), pet.repeat(1, rep).contiguous()  # column c reads c % Nf
-        if fd is not None:
-            if fd.K and fd.shape != (fd.K, int(precip.shape[0]), int(precip.shape[1])):
-                raise LgarError("forcing_directions hold %s, the forcing is [T, B] = %s: d_precip / d_pet must be [K, T, B]"
-                                % (fd.shape, tuple(precip.shape)))
-        if start is not None:
-            eng.restore(start)  # (in place of the fresh state the constructor left)
+        eng, precip, pet, fmap, check, state_out, status_out = _open_run(ctx, alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, engine_kw)
         out = eng.forward(precip, pet, series=("runoff", "percolation"), check=check, forcing_map=fmap)
         if state_out is not None:
             state_out.append(eng.snapshot())
         if status_out is not None:
             status_out.append(eng.status)
-        ctx.engine = eng
-        ctx.forcing = (precip, pet)
-        ctx.forcing_map = fmap
-        ctx.start = start
-        ctx.forcing_directions = fd
-        ctx.in_dtypes = (alpha.dtype, n.dtype, ksat.dtype)
-        ctx.check = check
-        ctx.status_out = status_out
         return out["runoff"], out["percolation"]
 
     @staticmethod
     def backward(ctx, g_runoff, g_perc):
-        eng = ctx.engine
-        precip, pet = ctx.forcing
-        wanted = [(kind, l) for ki, kind in enumerate(KINDS) if ctx.needs_input_grad[ki] for l in range(eng.L)]
-        # columns that already faulted in the forward run are the caller's to mask (status_out); they carry no gradient
-        fwd_bad = (eng.status & ST_FAULT_MASK) != 0
-        keep = (~fwd_bad).to(g_runoff.dtype)[None, :] if g_runoff is not None else None
-        gr = None if g_runoff is None else g_runoff * keep
-        gp = None if g_perc is None else g_perc * ((~fwd_bad).to(g_perc.dtype)[None, :])
-        fd = ctx.forcing_directions
-        # the forcing's parameters ride as K more lanes per column in the same groups: one batch of launches
-        wanted += [("forcing", k) for k in range(fd.K if fd is not None else 0) if ctx.needs_input_grad[9 + k]]
-        vj, st = parameter_vjp(eng, precip, pet, gr, gp, wanted, check=False, forcing_map=ctx.forcing_map, start=ctx.start,
-                               forcing_directions=fd)
-        st = torch.where(fwd_bad, torch.zeros_like(st), st)
-        if ctx.status_out is not None:
-            ctx.status_out.append(st)  # [forward status, tangent status]
-        if ctx.check and bool((st != 0).any()):
-            raise LgarStatusError("%d columns faulted in the tangent (gradient) integration" % int((st != 0).sum().item()))
-        grads = []
-        for ki, kind in enumerate(KINDS):
-            if not ctx.needs_input_grad[ki]:
-                grads.append(None)
-                continue
-            g = torch.stack([vj[(kind, l)] for l in range(eng.L)])
-            g = torch.where(fwd_bad[None, :], torch.zeros_like(g), g)
-            grads.append(g.to(ctx.in_dtypes[ki]))
-        return (*grads, None, None, None, None, None, None, *_forcing_parameter_grads(ctx, fd, vj, fwd_bad))
+        grads, forcing_grads = _series_backward(ctx, g_runoff, g_perc, 9)
+        return (*grads, None, None, None, None, None, None, *forcing_grads)
 
 
-def _forcing_parameter_grads(ctx, fd, vj, fwd_bad):
+def _series_backward(ctx, g_runoff, g_perc, first_forcing_input, moisture=None):
+    """What the backward passes of the series nodes do alike: the incoming gradients masked where the forward run faulted, one
+    parameter_vjp over the wanted (kind, layer) and forcing lanes, its status reported, the gradients gathered.  Returns
+    ([d alpha, d n, d ksat] each [L, N] or None, the gradients of forcing_directions.params).  first_forcing_input: where the
+    forcing parameters stand among the node's inputs.  moisture: parameter_vjp's (None: launch for launch what it was)."""
+    eng = ctx.engine
+    precip, pet = ctx.forcing
+    wanted = [(kind, l) for ki, kind in enumerate(KINDS) if ctx.needs_input_grad[ki] for l in range(eng.L)]
+    # columns that already faulted in the forward run are the caller's to mask (status_out); they carry no gradient
+    fwd_bad = (eng.status & ST_FAULT_MASK) != 0
+    keep = (~fwd_bad).to(g_runoff.dtype)[None, :] if g_runoff is not None else None
+    gr = None if g_runoff is None else g_runoff * keep
+    gp = None if g_perc is None else g_perc * ((~fwd_bad).to(g_perc.dtype)[None, :])
+    fd = ctx.forcing_directions
+    # the forcing's parameters ride as K more lanes per column in the same groups: one batch of launches
+    wanted += [("forcing", k) for k in range(fd.K if fd is not None else 0) if ctx.needs_input_grad[first_forcing_input + k]]
+    more = {} if moisture is None else dict(moisture=moisture)
+    vj, st = parameter_vjp(eng, precip, pet, gr, gp, wanted, check=False, forcing_map=ctx.forcing_map, start=ctx.start,
+                           forcing_directions=fd, **more)
+    st = torch.where(fwd_bad, torch.zeros_like(st), st)
+    if ctx.status_out is not None:
+        ctx.status_out.append(st)  # [forward status, tangent status]
+    if ctx.check and bool((st != 0).any()):
+        raise LgarStatusError("%d columns faulted in the tangent (gradient) integration" % int((st != 0).sum().item()))
+    grads = []
+    for ki, kind in enumerate(KINDS):
+        if not ctx.needs_input_grad[ki]:
+            grads.append(None)
+            continue
+        g = torch.stack([vj[(kind, l)] for l in range(eng.L)])
+        g = torch.where(fwd_bad[None, :], torch.zeros_like(g), g)
+        grads.append(g.to(ctx.in_dtypes[ki]))
+    return grads, _forcing_parameter_grads(ctx, fd, vj, fwd_bad, first_forcing_input)
+
+
+def _forcing_parameter_grads(ctx, fd, vj, fwd_bad, first_forcing_input=9):
     """d loss / d params[k] of a ForcingDirections from the columns' shares vj[("forcing", k)] [N]: with a forcing_map the columns
     of a cell are summed in the fixed order of CatchmentMap.sums (its bits, whatever the launch), with [T, N] forcing a column is
     its own cell; a scalar parameter gets the sum over the cells."""
     if fd is None:
         return ()
     eng = ctx.engine
-    ks = [k for k in range(fd.K) if ctx.needs_input_grad[9 + k]]
+    ks = [k for k in range(fd.K) if ctx.needs_input_grad[first_forcing_input + k]]
     cells = {}
     if ks:
         shares = torch.stack([torch.where(fwd_bad, torch.zeros_like(vj[("forcing", k)]), vj[("forcing", k)]) for k in ks])
@@ -248,6 +312,63 @@ def lgar_series(alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, **engi
     if fd is not None and not isinstance(fd, ForcingDirections):
         raise LgarError("forcing_directions must be a forcing.ForcingDirections; got %s" % type(fd).__name__)
     return LgarSeriesFunction.apply(alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, engine_kw, *(fd.params if fd is not None else ()))
+
+
+class LgarMoistureSeriesFunction(torch.autograd.Function):
+    """LgarSeriesFunction with the depth-binned soil moisture after every `every` rows as a third output
+    ([T // every, bins, N]); differentiable in what LgarSeriesFunction is differentiable in."""
+
+    @staticmethod
+    def forward(ctx, alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, bins, engine_kw, *forcing_params):
+        every, edges, what = bins
+        eng, precip, pet, fmap, check, state_out, status_out = _open_run(ctx, alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, engine_kw)
+        out = eng.run_with_soil_moisture(precip, pet, every, edges, what, series=("runoff", "percolation"), check=check, forcing_map=fmap)
+        if state_out is not None:
+            state_out.append(eng.snapshot())
+        if status_out is not None:
+            status_out.append(eng.status)
+        ctx.bins = (int(every), edges, what)
+        return out["runoff"], out["percolation"], out["soil_moisture"]
+
+    @staticmethod
+    def backward(ctx, g_runoff, g_perc, g_moist):
+        eng = ctx.engine
+        every, edges, what = ctx.bins
+        S, D = int(ctx.forcing[0].shape[0]) // every, eng.L if edges is None else len(edges) - 1
+        if g_moist is None:
+            cot = torch.zeros(S, D, eng.N, dtype=torch.float64, device=eng.device)
+        else:
+            # fp64, and nothing for the columns that faulted in the forward run (a select: their leftover state may have made a
+            # NaN of the snapshot and of its cotangent); a bin below the column is skipped inside the contraction
+            fwd_bad = (eng.status & ST_FAULT_MASK) != 0
+            cot = g_moist.to(eng.device, torch.float64)
+            cot = torch.where(fwd_bad[None, None, :], torch.zeros_like(cot), cot).contiguous()
+        grads, forcing_grads = _series_backward(ctx, g_runoff, g_perc, 10, moisture=(every, edges, what, cot))
+        return (*grads, None, None, None, None, None, None, None, *forcing_grads)
+
+
+def lgar_moisture_series(alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, every, edges=None, what="theta", **engine_kw):
+    """lgar_series with the soil-moisture profile as a third, differentiable output: returns (runoff [T, N], percolation [T, N],
+    moisture [T // every, D, N]), moisture[s] being LgarEngine.soil_moisture(edges, what) of the state after row
+    (s + 1) * every - 1 (edges: [D + 1] depths in cm, None = each column's own layers; what: "theta" or "storage").
+    engine_kw: what lgar_series takes (forcing_map, initial_state, state_out, check, status_out, forcing_directions, LgarEngine's).
+
+    Forward: LgarEngine.run_with_soil_moisture's windows -- the moisture has its bits, the two series lgar_series' bits.
+    Backward: every group of directions parameter_vjp forms goes through LgarEngine.tangent_window in windows of `every` rows, the
+    tangent state carried; after window s, LgarEngine.soil_moisture_tangent contracts snapshot s's cotangent (taken as fp64, zero
+    for columns that faulted in the forward run) with the tangent of the bins into the carried gradient.  A trailing T % every
+    rows form a last window without a snapshot.  Gradients reach alpha, n, ksat and forcing_directions.params as in lgar_series;
+    theta_e, theta_r, the thickness and the initial state are constants.  A bin wholly below the column reads NaN with
+    what="theta": its cotangent contributes nothing, whatever it holds (mask such entries out of a loss, or a NaN loss results
+    from the values themselves).
+    Catchment means compose: lg.catchment_sum(moisture[s], cmap) (CatchmentMap.sums over the [D, N] rows of one snapshot, with
+    area weights) gives [D, B] catchment moisture, which CatchmentScore takes against satellite or in-situ observations; its
+    gradient comes back through this node."""
+    fd = engine_kw.get("forcing_directions")
+    if fd is not None and not isinstance(fd, ForcingDirections):
+        raise LgarError("forcing_directions must be a forcing.ForcingDirections; got %s" % type(fd).__name__)
+    return LgarMoistureSeriesFunction.apply(alpha, n, ksat, theta_e, theta_r, thickness, precip, pet, (every, edges, what), engine_kw,
+                                            *(fd.params if fd is not None else ()))
 
 
 class _ChunkFunction(torch.autograd.Function):

@@ -14,7 +14,7 @@ LAYERS = (2, 3, 4, 5, 6)  # LGAR_LAYERS (csrc/lgar_plan.hpp): one translation un
 UNITS = [("lgar_kernels.hip", [], ""), ("lgar_probe.hip", [], ""), ("lgar_moisture.hip", [], ""), ("lgar_catchment.hip", [], ""),
          ("lgar_route.hip", [], ""), ("lgar_score.hip", [], ""), ("lgar_network.hip", [], ""), ("lgar_baseflow.hip", [], ""),
          ("lgar_network_mc.hip", [], ""), ("lgar_network_pool.hip", [], ""), ("lgar_snow.hip", [], ""), ("lgar_canopy.hip", [], ""),
-         ("lgar_leaf_tangent.hip", [], "")] + \
+         ("lgar_leaf_tangent.hip", [], ""), ("lgar_moisture_tangent.hip", [], "")] + \
         [("lgar_kernels_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS] + \
         [("lgar_tangent_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS] + \
         [("lgar_tangent_forced_nl.hip", ["-DLGAR_NL=%d" % n], "_%d" % n) for n in LAYERS]

@@ -603,10 +603,12 @@ class LgarEngine:
                     to_bottom=(fl >> 7).astype("int8"), n_fronts=self.n_fronts.cpu().numpy())
 
     # ------------------------------------------------------------------------------------------
-    def _moisture_bins(self, edges, what):
+    def _moisture_bins(self, edges, what, need_state=True):
         """Host-side checks of soil_moisture's bins (the library never reads device memory on the host, so the C-ABI takes the
-        caller's word for the edges): returns (device fp64 edges or None, number of bins)."""
-        self._need_state()
+        caller's word for the edges): returns (device fp64 edges or None, number of bins).  need_state=False: the bins are for
+        a state that is not this engine's own (soil_moisture_tangent)."""
+        if need_state:
+            self._need_state()
         if what not in _capi.MOIST_WHAT:
             raise LgarError("what must be 'theta' or 'storage' (got %r)" % (what,))
         if edges is None:
@@ -666,6 +668,48 @@ class LgarEngine:
             raise LgarError("weights are used by the basin sums only: pass basin=True")
         self._moisture_launch(e_dev, D, what, out, w, sums)
         return out if sums is None else (out, sums)
+
+    def _moisture_tangent_launch(self, tstate, e_dev, n_bins, what, out, cot, group):
+        """lgar_soil_moisture_tangent over a checked TangentState and checked bins: `out`, or `cot` into tstate.grad."""
+        vs, ts = tstate.value._struct(), tstate._struct()
+        self._call("soil_moisture_tangent", C.byref(self.dims), C.byref(self._params), C.byref(vs), C.byref(ts), _ptr(e_dev), n_bins,
+                   _capi.MOIST_WHAT[what], _ptr(out), _ptr(cot), int(group), None if cot is None else tstate.grad.data_ptr())
+
+    def soil_moisture_tangent(self, tstate, edges=None, what="theta", cot=None, group=1):
+        """The tangent of soil_moisture() along the direction a TangentState was integrated for (lgar_soil_moisture_tangent,
+        include/lgar.h): a pure function of the state `tangent_window` handed back as `end`, computed on
+        the device.  The engine is the one whose tangent_window made the state: its N columns are the state's M lanes.
+
+        edges, what: soil_moisture()'s; the tangent of a bin wholly below the column is 0 (its value is NaN).
+        cot=None: returns the [D, M] tangent in the engine's dtype (fp64 arithmetic, rounded once).
+        cot: a contiguous fp64 [D, M // group] cotangent on the device -- lane c reads column c // group, the forcing_group
+        convention of the tangent launches.  The contraction sum_i cot[i] * tangent[i] (unrounded fp64 tangents, i ascending, bins
+        below the column skipped whatever their cotangent holds) is ADDED to tstate.grad in place, no [D, M] array is allocated,
+        and tstate is returned: the next window of the same direction carries the sum on."""
+        e_dev, D = self._moisture_bins(edges, what, need_state=False)
+        if not isinstance(tstate, TangentState):
+            raise LgarError("tstate must be a TangentState (the `end` of LgarEngine.tangent_window); got %s" % type(tstate).__name__)
+        self._check_state(tstate.value, "tstate")
+        for nm in ("depth", "theta"):
+            t = tstate.tangent.get(nm)
+            if (not isinstance(t, torch.Tensor) or tuple(t.shape) != (self.front_slots, self.N) or t.dtype != self.dtype
+                    or t.device != self.status.device or not t.is_contiguous()):
+                raise LgarError("tstate.tangent[%r] must be a contiguous [%d, %d] %s tensor on %s" % (nm, self.front_slots, self.N, self.dtype, self.device))
+        group = int(group)
+        if group < 1 or self.N % group != 0:
+            raise LgarError("group must be >= 1 and divide the %d lanes of the state (got %d)" % (self.N, group))
+        if cot is None:
+            out = torch.empty(D, self.N, dtype=self.dtype, device=self.device)
+            self._moisture_tangent_launch(tstate, e_dev, D, what, out, None, group)
+            return out
+        if (not isinstance(cot, torch.Tensor) or tuple(cot.shape) != (D, self.N // group) or cot.dtype != torch.float64
+                or cot.device != self.status.device or not cot.is_contiguous()):
+            raise LgarError("cot must be a contiguous fp64 [%d, %d] tensor on %s" % (D, self.N // group, self.device))
+        g = tstate.grad
+        if tuple(g.shape) != (self.N,) or g.dtype != self.dtype or g.device != self.status.device or not g.is_contiguous():
+            raise LgarError("tstate carries a gradient of %s %s, this engine needs [%d] %s" % (tuple(g.shape), g.dtype, self.N, self.dtype))
+        self._moisture_tangent_launch(tstate, e_dev, D, what, None, cot, group)
+        return tstate
 
     def run_with_soil_moisture(self, precip, pet, every, edges=None, what="theta", series=("runoff", "percolation"), basin=(),
                                weights=None, check=True, forcing_group=1, forcing_map=None):
